@@ -25,7 +25,13 @@ max-over-ranks time and the result reductions are the only collectives.  `--gpus
 torch.distributed environment starts N ranks itself (a torch.distributed.run child process, before
 this process touches the GPU) and exits with its status.
 
-Also reported:
+A plain run (`--gpus N --steps K --warmup W`) generates the input, warms up, times the K steps and
+prints one JSON line: metric, value, unit, ms_per_step (milliseconds of one timed step), the workload
+and the per-stage times of the timed steps with the roofline computed from them.  `--dump-outputs DIR`
+also writes what the last timed step returned to its caller (see dump_outputs).  Everything else below
+takes runs of its own and is measured only with `--full`, after the timed region.
+
+Reported (all but the roofline only with --full):
   byte_diff      differing bytes between the GPU blocks and the reference's output for the same
                  blocks (oracle/_ref/smallz4, the reference CLI compiled from its sources, one child
                  process per block with a hard deadline; the C restatement when _ref is absent):
@@ -127,6 +133,12 @@ def parse_args(argv=None):
     ap.add_argument("--mb", type=float, default=None, help="override: input MB (1e6 bytes) per rank")
     ap.add_argument("--block-size", type=int, default=None, help="override the workload's block size")
     ap.add_argument("--level", type=int, default=9)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: byte diff against the reference, device "
+                         "round trip, CPU baseline, stream, dictionary, levels and shapes (the options "
+                         "below tune or skip single legs of a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (frame size, frame bytes) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of each CPU baseline sample")
     ap.add_argument("--verify-threads", type=int, default=POOL)
     ap.add_argument("--verify-seconds", type=float, default=20.0,
@@ -149,6 +161,8 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: gloo ranks compress their shards with the oracle (tests the sharding)")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.workload is None:
         a.workload = "enwik8" if a.gpus == 1 else "enwik9"
     return a
@@ -326,6 +340,44 @@ def valu_ceiling():
         return None
     out.update({"vgpr": round(best / 1024 / (CLOCK_GHZ * 1e9), 4), "clock_ghz": CLOCK_GHZ, "variant": "add_xor"})
     return out
+
+
+DUMP_SAMPLE = 4 << 20  # frame bytes written in full up to this size, a seeded sample of as many above it
+DUMP_CHUNK = 4096      # frame bytes per entry of the chunk sums
+DUMP_SEED = 2025     # of the sample positions
+
+
+def dump_outputs(dirname: str, frame, rank: int, world: int):
+    """--dump-outputs: what the last timed step handed to its caller -- this rank's frame (at N>1 its
+    part of it) and its size -- as .npy files (the names carry _rank<r> at N>1), about 17 MB at most:
+      frame_size.npy        float64 [1]: bytes of the frame
+      frame_sample.npy      float32: the frame's bytes, all of them up to DUMP_SAMPLE, else those at
+                            DUMP_SAMPLE positions drawn with a fixed seed from [0, size)
+      frame_chunk_sums.npy  float64 [chunks, 2]: per DUMP_CHUNK bytes of the whole frame, the sum of the
+                            bytes and the sum of (offset in chunk + 1) x byte (both exact), so that a
+                            change outside the sample shows as well
+    The inputs are seeded, so two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    n = int(frame.size)
+    np.save(os.path.join(dirname, f"frame_size{sfx}.npy"), np.array([n], dtype=np.float64))
+    if n > DUMP_SAMPLE:
+        sample = frame[np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE))]
+    else:
+        sample = frame
+    np.save(os.path.join(dirname, f"frame_sample{sfx}.npy"), sample.astype(np.float32))
+    rows = -(-n // DUMP_CHUNK)
+    x = np.zeros(rows * DUMP_CHUNK, dtype=np.uint8)
+    x[:n] = frame
+    x = x.reshape(rows, DUMP_CHUNK)
+    w = np.arange(1, DUMP_CHUNK + 1, dtype=np.float64)
+    sums = np.empty((rows, 2), dtype=np.float64)
+    for i in range(0, rows, 1024):  # float64 in pieces: every product and sum is an integer below 2^53
+        xf = x[i:i + 1024].astype(np.float64)
+        sums[i:i + 1024, 0] = xf.sum(axis=1)
+        sums[i:i + 1024, 1] = xf @ w
+    np.save(os.path.join(dirname, f"frame_chunk_sums{sfx}.npy"), sums)
 
 
 def summary_line(rec) -> str:
@@ -642,19 +694,24 @@ def main():
     header = "smallz4" if world == 1 else "none"
     barrier = dist.barrier if world > 1 else None
     elapsed, stages, size, out, t_in = run.compress(data, bs, chain, args.steps, args.warmup, header, barrier)
-    part = out[:size].cpu().numpy().tobytes()
-    blocks = part[7:-4] if header == "smallz4" else part
+    full = args.full
+    # what the last timed step wrote, on the host: only for the dump and the reference diff
+    frame = out[:size].cpu().numpy() if (args.dump_outputs or full) else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, frame, rank, world)
 
     # device round trip of this rank's part (outside the timed region)
     rt_ok, dec = True, None
-    if not args.no_decode and nbytes:
+    if full and not args.no_decode and nbytes:
         rt_ok, dec = run.roundtrip(out, size, header, t_in)
     del out, t_in
     torch.cuda.empty_cache()
 
     # output-byte diff against the reference: every block at N=1 on enwik8, else a sample bounded in time
     ver = {"byte_diff": -1, "blocks_verified": 0, "verified_against": None}
-    if not args.no_verify and nbytes:
+    if full and not args.no_verify and nbytes:
+        part = frame.tobytes()
+        blocks = part[7:-4] if header == "smallz4" else part
         every = world == 1 and args.workload == "enwik8"
         ver = verify_sample(blocks, data, bs, chain, args.verify_threads, 600.0 if every else args.verify_seconds, every)
 
@@ -673,17 +730,18 @@ def main():
         frame_bytes, diff, verified, rt_bad = size, ver["byte_diff"], ver["blocks_verified"], 0 if rt_ok else 1
 
     stream_leg = dict_leg = None
-    if world == 1 and not args.no_stream and nbytes:
+    if full and world == 1 and not args.no_stream and nbytes:
         stream_leg = stream_big_leg(data, args.stream_reps)
-    if world == 1 and not args.no_dict and args.level == 9:
+    if full and world == 1 and not args.no_dict and args.level == 9:
         dict_leg = dictionary_leg(run, args.no_verify)
 
     levels = None
-    if world == 1 and not args.no_levels and args.level == 9 and args.workload == "enwik8" and not args.mb and nbytes:
+    if (full and world == 1 and not args.no_levels and args.level == 9 and args.workload == "enwik8" and not args.mb
+            and nbytes):
         levels = levels_leg(args, run, data, bs)
 
     shapes = None
-    if world == 1 and not args.no_shapes and args.level == 9 and args.workload == "enwik8" and not args.mb:
+    if full and world == 1 and not args.no_shapes and args.level == 9 and args.workload == "enwik8" and not args.mb:
         shapes = shapes_leg(args, run, chain, data)
 
     if rank == 0:
@@ -756,15 +814,15 @@ def main():
             "data": wl[1],
             "config": cfg,
             "value_per_gpu": round(value / world, 2),
-            "byte_diff": diff,
-            "blocks_verified": verified,
-            "verified_against": ver.get("verified_against"),
-            "verify": {k: v for k, v in ver.items() if k.startswith("verify") or k == "blocks_total"},
-            "roundtrip_ok": rt_bad == 0,
             "compression_ratio": round(frame_bytes / total, 5) if total else None,
             "stages_ms": {k: round(v, 3) for k, v in stages.items()},
+            # from the timed steps' stage times and the committed profile records: no run of its own
             "roofline": roof,
         }
+        if full:
+            rec.update({"byte_diff": diff, "blocks_verified": verified, "verified_against": ver.get("verified_against"),
+                        "verify": {k: v for k, v in ver.items() if k.startswith("verify") or k == "blocks_total"},
+                        "roundtrip_ok": rt_bad == 0})
         if dec is not None:
             rec["unlz4"] = dec
         if stream_leg is not None:
@@ -775,10 +833,12 @@ def main():
             rec["levels"] = levels
         if shapes is not None:
             rec["shapes"] = shapes
-        # the reference on this host's cores, rank 0, after the timed region (at every N)
-        rec["cpu_baseline"] = cpu_baseline(data, bs, chain, args.cpu_seconds)
+        if full:
+            # the reference on this host's cores, rank 0, after the timed region (at every N)
+            rec["cpu_baseline"] = cpu_baseline(data, bs, chain, args.cpu_seconds)
         print(json.dumps(rec), flush=True)
-        print(summary_line(rec), flush=True)
+        if full:
+            print(summary_line(rec), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -14,13 +14,13 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 if [ -z "${SKIP_BENCH:-}" ]; then
-  timeout -k 10 700 python3 "$R/bench.py" $EXTRA > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 700 python3 "$R/bench.py" --full $EXTRA > "$OUT/bench.json" 2> "$OUT/bench.err"
 fi
 cd /tmp
-ARGS="--steps 10 --warmup 3 --no-verify --no-stream --no-dict --no-shapes --no-levels --cpu-seconds 0.5 $EXTRA"
+ARGS="--full --steps 10 --warmup 3 --no-verify --no-stream --no-dict --no-shapes --no-levels --cpu-seconds 0.5 $EXTRA"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- \
   python3 "$R/bench.py" $ARGS > "$OUT/trace.log" 2>&1
-ARGS="--steps 3 --warmup 1 --no-verify --no-decode --no-stream --no-dict --no-shapes --no-levels --cpu-seconds 0.5 $EXTRA"
+ARGS="--full --steps 3 --warmup 1 --no-verify --no-decode --no-stream --no-dict --no-shapes --no-levels --cpu-seconds 0.5 $EXTRA"
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o bench -- \
   python3 "$R/bench.py" $ARGS > "$OUT/fetch.log" 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -o bench -- \

@@ -326,8 +326,13 @@ def test_reference_cli_rebuilt_on_dropin(tmp_path):
     src.write_bytes(synth.enwik8_like(6 << 20, seed=19))
     dic = tmp_path / "dict.txt"
     dic.write_bytes(synth.enwik8_like(30000, seed=20))
+    # oracle/_ref may have been built in another copy of the tree and brought here (a link to it
+    # included), so the binary's own search path is not relied on: it runs on this tree's HIP library
+    libdir = os.path.join(ROOT, "smallz4_amd", "lib")
+    env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(
+        [libdir] + [p for p in os.environ.get("LD_LIBRARY_PATH", "").split(os.pathsep) if p]))
     for flags in (["-9"], ["-6"], ["-2"], ["-0"], ["-9", "-l"], ["-D", str(dic), "-9"]):
         a, b = tmp_path / "a.lz4", tmp_path / "b.lz4"
-        subprocess.run([amd, "-f", *flags, str(src), str(a)], check=True)
+        subprocess.run([amd, "-f", *flags, str(src), str(a)], check=True, env=env)
         subprocess.run([ref, "-f", *flags, str(src), str(b)], check=True)
         assert a.read_bytes() == b.read_bytes(), flags

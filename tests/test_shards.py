@@ -176,7 +176,7 @@ def test_bench_two_ranks_shard_one_input(workload, mb, sample):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SZ4_BENCH_SHARE_DEVICE="1")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", workload,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--workload", workload,
                         "--mb", str(mb), "--steps", "2", "--warmup", "1", "--verify-seconds", "15",
                         "--cpu-seconds", "1", "--no-stream"], capture_output=True, text=True, timeout=400, cwd=root,
                        env=env)
