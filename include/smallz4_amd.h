@@ -87,6 +87,48 @@ int sz4_compress_blocks_device(sz4_ctx* ctx, const void* d_in, uint64_t n, uint3
  * number of blocks, or a negative status. */
 int64_t sz4_last_block_sizes(sz4_ctx* ctx, uint32_t* sizes, uint64_t max_blocks);
 
+/* ---- ragged batch: many separate buffers of different sizes ------------------------------------
+ * Worst-case output of sz4_compress_batch_device: the sum over the items of (size + 4) -- stored blocks
+ * are never larger than their input. */
+uint64_t sz4_batch_bound(const uint32_t* sizes, uint64_t count);
+
+/* Compress `count` separate device buffers, each 0 .. 4 MiB, each as one LZ4 block on its own: item i's
+ * output (4-byte size word + payload, the word's top bit set when the item is stored) is exactly what
+ * smallz4::lz4 emits for that buffer alone; an empty item produces no bytes.  The blocks land back to
+ * back in d_out in caller order, as bare blocks (what SZ4_HEADER_NONE writes).  The items are staged by
+ * one gather kernel per internal piece (any source alignment; nothing is read outside the aligned
+ * 16-byte words that overlap an item) and compressed in pieces of whole items: at most
+ * sz4_set_batch_chunk bytes (capped and retried as in sz4_compress_blocks_device) and at most 32768
+ * items each.  Items above 64 KiB are compressed in a pipeline run of their own inside their piece, so
+ * one large item does not slow the small ones down.  No dictionary, no linked items.
+ *
+ *   in_ptrs      HOST array of count DEVICE pointers (may be NULL where the size is 0)
+ *   in_sizes     HOST array of count sizes; one above 4 MiB: SZ4_E_ARG before any work
+ *   max_chain    reference maxChainLength (0..65535)
+ *   d_out        device pointer; out_cap < sz4_batch_bound: SZ4_E_CAPACITY before any work
+ *   out_offsets  HOST array of count + 1: item i occupies d_out[out_offsets[i], out_offsets[i + 1])
+ *   stream       hipStream_t (NULL = default stream); the call returns after the stream has finished
+ * sz4_last_block_sizes then reports one size per item (0 for an empty item), in caller order. */
+int sz4_compress_batch_device(sz4_ctx* ctx, const void* const* in_ptrs, const uint32_t* in_sizes, uint64_t count,
+                              uint32_t max_chain, void* d_out, uint64_t out_cap, uint64_t* out_offsets,
+                              void* stream);
+
+/* Device time (milliseconds) of the gather kernels of the last sz4_compress_batch_device call (with
+ * sz4_set_timing on; it is not part of any sz4_last_stage_ms stage). */
+float sz4_last_gather_ms(sz4_ctx* ctx);
+
+/* The reverse: item i is the bare block d_blocks[offsets[i], offsets[i + 1]) (HOST array of count + 1;
+ * a non-empty item is its 4-byte size word + payload) and decodes to d_out[out_offsets[i],
+ * out_offsets[i + 1]) (HOST array of count + 1) -- exactly what the reference decoder gives for a frame
+ * holding that block alone.  Items are independent: a match that reaches below its item's first output
+ * byte reads zeros (the reference's zero-initialised history), never another item's output.  One
+ * wavefront decodes one item.
+ * d_out == NULL / out_cap == 0 queries the sizes: out_offsets is filled and SZ4_E_CAPACITY returned, as
+ * sz4_unlz4 does.  SZ4_E_CORRUPT: an item whose size word disagrees with its extent, a non-empty item
+ * shorter than 4 bytes, a malformed block (see sz4_unlz4). */
+int sz4_unlz4_batch_device(sz4_ctx* ctx, const void* d_blocks, const uint64_t* offsets, uint64_t count,
+                           void* d_out, uint64_t out_cap, uint64_t* out_offsets, void* stream);
+
 /* Whole-stream compression with the exact semantics of
  * smallz4::lz4(getBytes, sendBytes, maxChainLength, dictionary, useLegacyFormat)
  * (reference smallz4.h:47-64): 4 MiB dependent blocks (8 MiB independent
@@ -122,7 +164,8 @@ int sz4_lz4_stream(sz4_ctx* ctx, sz4_get_bytes get_bytes, sz4_send_bytes send_by
  * as many frame bytes); rounded down to whole blocks, at least one.  0 restores the 64 MiB default. */
 void sz4_set_stream_chunk(sz4_ctx* ctx, uint64_t bytes);
 
-/* Input bytes per internal piece of sz4_compress_blocks_device (whole blocks, at least one); the
+/* Input bytes per internal piece of sz4_compress_blocks_device and sz4_compress_batch_device (whole
+ * blocks / items, at least one); the
  * device scratch is about 36-50 bytes per piece byte.  An explicit size is not capped by free memory.
  * 0 restores the default (448 MiB, capped by free memory). */
 void sz4_set_batch_chunk(sz4_ctx* ctx, uint64_t bytes);

@@ -10,6 +10,8 @@ plus the data-parallel entry point the GPU is built for:
 
     Compressor().compress_blocks(data, block_size=65536, max_chain_length=65535)
         -> frame whose every block equals smallz4's output for that block alone
+    Compressor().compress_batch(items, max_chain_length=65535) / unlz4_batch(blocks)
+        -> many separate buffers of different sizes, one independently decodable LZ4 block each
 
 All compression runs in the HIP library smallz4_amd/lib/libsmallz4_amd.so; there
 is no CPU fallback.
@@ -179,6 +181,97 @@ class Compressor:
                                            block_size, max_chain_length, header, stream)
         return out[:size].cpu().numpy().tobytes()
 
+    # -- ragged batch: many separate buffers, one LZ4 block each ---------------------------------
+    def compress_batch_device(self, ptrs, sizes, d_out: int, out_cap: int, max_chain_length: int = MaxChainLength,
+                              stream: int = 0) -> list[int]:
+        """Device pointers and sizes of the items in, the blocks' offsets in d_out (len(sizes) + 1) out
+        (see sz4_compress_batch_device): item i is d_out[off[i]:off[i + 1]], empty for an empty item."""
+        count = len(sizes)
+        if len(ptrs) != count:
+            raise ValueError("ptrs and sizes differ in length")
+        p = (ctypes.c_void_p * max(count, 1))(*[int(x) or None for x in ptrs])
+        z = (ctypes.c_uint32 * max(count, 1))(*[int(x) for x in sizes])
+        off = (ctypes.c_uint64 * (count + 1))()
+        rc = self._lib.sz4_compress_batch_device(self._h, p, z, count, int(max_chain_length), ctypes.c_void_p(d_out),
+                                                 out_cap, off, ctypes.c_void_p(stream))
+        self._check(rc, "sz4_compress_batch_device")
+        return list(off)
+
+    def batch_bound(self, sizes) -> int:
+        """Worst-case output bytes of compress_batch_device for these item sizes (sz4_batch_bound)."""
+        z = (ctypes.c_uint32 * max(len(sizes), 1))(*[int(x) for x in sizes])
+        return int(self._lib.sz4_batch_bound(z, len(sizes)))
+
+    def unlz4_batch_device(self, d_blocks: int, offsets, d_out: int, out_cap: int, stream: int = 0) -> list[int]:
+        """Bare blocks d_blocks[offsets[i]:offsets[i + 1]] in, each decoded on its own into d_out; returns
+        the output offsets (see sz4_unlz4_batch_device).  d_out = 0, out_cap = 0 queries the offsets."""
+        count = len(offsets) - 1
+        if count < 0:
+            raise ValueError("offsets needs count + 1 entries")
+        o = (ctypes.c_uint64 * (count + 1))(*[int(x) for x in offsets])
+        res = (ctypes.c_uint64 * (count + 1))()
+        rc = self._lib.sz4_unlz4_batch_device(self._h, ctypes.c_void_p(d_blocks), o, count, ctypes.c_void_p(d_out), out_cap,
+                                              res, ctypes.c_void_p(stream))
+        if not (rc == _native.SZ4_E_CAPACITY and not d_out and not out_cap):
+            self._check(rc, "sz4_unlz4_batch_device")
+        return list(res)
+
+    def compress_batch(self, items, max_chain_length: int = MaxChainLength) -> list[bytes]:
+        """Every item (bytes-like, or a uint8 torch tensor) compressed as one LZ4 block on its own:
+        [oz_block(item) for item in items], in one call.  A device tensor is used in place, whatever its
+        storage offset; host items go up in one transfer."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        views = [None] * len(items)
+        host = []
+        for i, it in enumerate(items):
+            if isinstance(it, torch.Tensor):
+                if it.dtype != torch.uint8:
+                    raise TypeError("tensor items must be uint8")
+                t = it.reshape(-1) if it.is_contiguous() else it.contiguous().reshape(-1)
+                views[i] = t if t.is_cuda and t.device == dev else t.to(dev)
+            else:
+                host.append((i, memoryview(it).cast("B")))
+        if host:
+            joined = bytearray().join(m for _, m in host)
+            up = (torch.frombuffer(joined, dtype=torch.uint8).to(dev) if joined
+                  else torch.empty(0, dtype=torch.uint8, device=dev))
+            at = 0
+            for i, m in host:
+                views[i] = up[at:at + len(m)]
+                at += len(m)
+        sizes = [v.numel() for v in views]
+        cap = self.batch_bound(sizes)
+        out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        off = self.compress_batch_device([v.data_ptr() if n else 0 for v, n in zip(views, sizes)], sizes,
+                                         out.data_ptr(), cap, max_chain_length, stream)
+        raw = out[:off[-1]].cpu().numpy().tobytes()
+        return [raw[off[i]:off[i + 1]] for i in range(len(sizes))]
+
+    def unlz4_batch(self, blocks) -> list[bytes]:
+        """The reverse of compress_batch: every bare block (size word + payload, b"" for an empty item)
+        decoded on its own, as the reference decoder reads a frame holding that block alone."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        blocks = [bytes(b) for b in blocks]
+        offsets = [0]
+        for b in blocks:
+            offsets.append(offsets[-1] + len(b))
+        joined = bytearray().join(blocks)
+        d = (torch.frombuffer(joined, dtype=torch.uint8).to(dev) if joined
+             else torch.empty(16, dtype=torch.uint8, device=dev))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        sizes = self.unlz4_batch_device(d.data_ptr(), offsets, 0, 0, stream)
+        out = torch.empty(max(sizes[-1], 16), dtype=torch.uint8, device=dev)
+        off = self.unlz4_batch_device(d.data_ptr(), offsets, out.data_ptr(), sizes[-1], stream)
+        raw = out[:off[-1]].cpu().numpy().tobytes()
+        return [raw[off[i]:off[i + 1]] for i in range(len(blocks))]
+
+    def last_gather_ms(self) -> float:
+        """Device time of the last compress_batch_device call's gather kernels (with set_timing on)."""
+        return float(self._lib.sz4_last_gather_ms(self._h))
+
     # -- decoder: the reference's smallz4cat -----------------------------------------------------
     def unlz4(self, frame: bytes, dictionary: bytes = b"") -> bytes:
         """smallz4cat's unlz4 (smallz4cat.c:112-360) on the GPU: the bytes `frame` decodes to.
@@ -268,7 +361,8 @@ class Compressor:
         return int(self._lib.sz4_dict_rounds(self._h))
 
     def unlz4_resolve_passes(self) -> int:
-        """Pointer-jumping passes of the last split-mode decode (0: decoded block by block)."""
+        """Longest reference chain (hops) the last split-mode decode followed while packing its output
+        (0: decoded block by block, or no byte referred to another sub-segment)."""
         return int(self._lib.sz4_unlz4_resolve_passes(self._h))
 
     def unlz4_index_parallel(self) -> bool:
@@ -308,3 +402,13 @@ def compress_blocks(data, block_size: int = 65536, max_chain_length: int = MaxCh
 def unlz4(frame: bytes, dictionary: bytes = b"") -> bytes:
     """smallz4cat's decoder (smallz4cat.c:112-360) on the GPU."""
     return _ctx().unlz4(frame, dictionary)
+
+
+def compress_batch(items, max_chain_length: int = MaxChainLength) -> list[bytes]:
+    """Every item compressed as one LZ4 block on its own (Compressor.compress_batch)."""
+    return _ctx().compress_batch(items, max_chain_length)
+
+
+def unlz4_batch(blocks) -> list[bytes]:
+    """Every bare block decoded on its own (Compressor.unlz4_batch)."""
+    return _ctx().unlz4_batch(blocks)

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("SMALLZ4_AMD_LIB") or os.path.join(os.path.dirname(os.
                                                                "libsmallz4_amd.so")
 
 SZ4_OK = 0
+SZ4_E_ARG = -1
 SZ4_E_CAPACITY = -3
 SZ4_E_CORRUPT = -6
 SZ4_HEADER_SMALLZ4 = 0
@@ -35,6 +36,11 @@ SIGNATURES = {
     "sz4_bound": (_u64, [_u64, _u32]),
     "sz4_compress_blocks_device": (_i32, [_vp, _vp, _u64, _u32, _u32, _i32, _vp, _u64, ctypes.POINTER(_u64), _vp]),
     "sz4_last_block_sizes": (ctypes.c_int64, [_vp, ctypes.POINTER(_u32), _u64]),
+    "sz4_batch_bound": (_u64, [ctypes.POINTER(_u32), _u64]),
+    "sz4_compress_batch_device": (_i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_u32), _u64, _u32, _vp, _u64,
+                                         ctypes.POINTER(_u64), _vp]),
+    "sz4_last_gather_ms": (ctypes.c_float, [_vp]),
+    "sz4_unlz4_batch_device": (_i32, [_vp, _vp, ctypes.POINTER(_u64), _u64, _vp, _u64, ctypes.POINTER(_u64), _vp]),
     "sz4_lz4": (_i32, [_vp, _vp, _u64, _u32, _vp, _u64, _i32, _vp, _u64, ctypes.POINTER(_u64)]),
     "sz4_lz4_bound": (_u64, [_u64, _i32]),
     "sz4_lz4_stream": (_i32, [_vp, GET_BYTES, SEND_BYTES, _u32, _vp, _u64, _i32, _vp]),

@@ -4,10 +4,12 @@
 // HBM (grow-only, so repeated calls allocate nothing), launches the kernel
 // pipeline of sz4_kernels.hip on one HIP stream and assembles the frame.
 //
-// Two job shapes:
+// Three job shapes:
 //   * independent blocks (sz4_compress_blocks_device): every block compressed
 //     as the reference compresses a stand-alone input -- the data-parallel
 //     shape that fills the GPU (BASELINE configs 1-4);
+//   * ragged batches (sz4_compress_batch_device): the same, over many separate
+//     device buffers of different sizes, one block each;
 //   * one reference stream (sz4_lz4): the exact block structure of
 //     smallz4::compress (smallz4.h:476-813): 4 MiB blocks that see the previous
 //     64 KiB, or 8 MiB independent legacy blocks.
@@ -233,6 +235,11 @@ struct sz4_ctx {
   DevBuf unBlk, unMeta, unFlags, unFrame, unDict, unOut, unSeq;  // decoder (sz4_unlz4*)
   DevBuf unSubs, unMasks, unImage;  // decoder split mode: sub-segments, their token-start masks, the u32 image
   DevBuf unIx;                       // decoder: the parallel frame index's candidates and successors
+  // ragged batch API: the gather's item table, the block mover's table and the staging area of a piece that
+  // runs as two pipeline runs (sz4_compress_batch_device); the batch decoder's extent table
+  DevBuf batchItems, batchMoves, batchTmp, unBatch;
+  hipEvent_t evGather[2] = {};  // timing: around k_batch_gather
+  float gatherMs = 0;
   bool unIndexSerial = getenv("SZ4_UNLZ4_INDEX") && atoi(getenv("SZ4_UNLZ4_INDEX")) == 0;  // A/B: the one-lane walk
   std::vector<UnBlock> hUn;
   std::vector<UnSub> hSub;
@@ -280,7 +287,7 @@ struct sz4_ctx {
             &dpSegs, &reach, &segState, &walkSegs, &walkState, &longFlag, &longBits, &segLong, &segTail, &dpRec, &work,
             &dictLast, &dictPrevH, &dictPrevX, &dictPH, &dictPE, &dictKeys, &dictTemp, &dictSc, &dictSnap, &dictRuns, &dictLz,
             &chunkOut[0], &chunkOut[1], &stagedS[0], &stagedS[1], &unBlk, &unMeta, &unFlags, &unFrame, &unDict,
-            &unOut, &unSeq, &unSubs, &unMasks, &unImage, &unIx};
+            &unOut, &unSeq, &unSubs, &unMasks, &unImage, &unIx, &batchItems, &batchMoves, &batchTmp, &unBatch};
   }
 
   int fail(int code, const char* what, hipError_t e = hipSuccess)
@@ -1293,6 +1300,162 @@ int stream_decompress(sz4_ctx* c, sz4_get_byte get, sz4_send_out send, const uin
   send(pend.data(), (unsigned int)pend.size(), user);
   return SZ4_OK;
 }
+
+// input bytes per internal pipeline run of the block entry points (sz4_compress_blocks_device,
+// sz4_compress_batch_device): batchChunk; under a device bound about 1/64 of the bound; else, unless set
+// explicitly, capped so that the scratch takes at most a quarter of the memory the context could use now
+uint64_t piece_bytes(sz4_ctx* c)
+{
+  uint64_t chunk = c->batchChunk;
+  if (c->budget.limit) {
+    chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(kPieceFloor, c->budget.limit / 64));
+  } else if (!c->batchChunkSet) {
+    size_t freeB = 0, totalB = 0;
+    if (hipMemGetInfo(&freeB, &totalB) == hipSuccess)
+      chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(kPieceFloor, (freeB + c->budget.used) / (4 * kScratchPerByte)));
+    else
+      (void)hipGetLastError();
+  }
+  return chunk;
+}
+
+// ---- ragged batch API (sz4_compress_batch_device) -------------------------------------------------
+// Every non-empty item is one Block of a ragged plan.  Layout in staging: the items of a pipeline run in
+// caller order, each at the next multiple of kBatchAlign (64) bytes; k_batch_gather zero-fills the gaps
+// and the kPad bytes after the last item.  Why that is safe is DESIGN section 4; in short, every kernel
+// addresses a block through its own start / end / low, the bytes past a block's end only ever feed 4-byte
+// reads whose excess is masked (in a uniform plan they are the next block's data), the last block still has
+// the largest end (the longBits clear), and 64-byte strides give every block at least 64 positions of the
+// per-position arrays that double as per-block records (24 bytes per block in `reach` during assembly).
+//
+// Blocks per pipeline run.  Besides ~50 bytes per staged byte a run needs per BLOCK: its interval slots
+// (kMaxIv x 32 = 4352 bytes), and in the shared region per parse or walk segment -- at least one each per
+// block -- the larger of the parse's side values (10 KiB), the greedy/lazy replay slots (11 KiB) and the
+// token-walk slots (8 KiB), plus ~300 bytes of descriptors: 16 KiB in all.  The cap keeps that at a quarter
+// of the piece's per-byte scratch, and at 512 MiB (32768 blocks) for the default piece.
+constexpr uint64_t kPerBlockScratch = 16384;
+constexpr uint64_t kBatchMaxBlocks = 32768;
+uint64_t batch_block_cap(uint64_t piece)
+{
+  return std::min<uint64_t>(kBatchMaxBlocks, std::max<uint64_t>(64, piece * kScratchPerByte / 4 / kPerBlockScratch));
+}
+
+uint64_t batch_stride(uint64_t size) { return (size + kBatchAlign - 1) / kBatchAlign * kBatchAlign; }
+
+// an item whose window fits the finders' LDS (finish_plan's test: the first segment's window is the whole
+// item, and no later segment's reaches further)
+bool batch_fits_lds(uint64_t size) { return (size + 8 + 3) / 4 * 4 <= find_lds_bytes(); }
+
+// One pipeline run over the items idx[0..k) (caller indices, ascending, all non-empty): plan, gather,
+// compress into out[0, outCap).  bytes[k] receives each item's blockBytes word (size with the 4-byte word,
+// top bit = stored); the blocks lie back to back in idx order.
+int batch_run(sz4_ctx* c, const std::vector<uint64_t>& idx, const void* const* ptrs, const uint32_t* sizes, uint32_t maxChain,
+              uint8_t* out, uint64_t outCap, std::vector<uint32_t>& bytes, hipStream_t s)
+{
+  const uint32_t nb = (uint32_t)idx.size();
+  std::vector<BatchItem> items(nb);
+  c->hBlocks.clear();
+  uint64_t at = 0;
+  for (uint32_t k = 0; k < nb; k++) {
+    const uint64_t n = sizes[idx[k]];
+    items[k] = BatchItem{(uint64_t)(uintptr_t)ptrs[idx[k]], at, n};
+    Block B{};
+    B.start = at;
+    B.end = at + n;
+    B.low = at;
+    B.cut = kNone;
+    B.prev = kNoBlock;
+    B.flags = 0;
+    c->hBlocks.push_back(B);
+    at += batch_stride(n);
+  }
+  finish_plan(c);
+  // the uniform plan caches describe another plan now: a following call of either kind plans again
+  c->planN = ~0ull;
+  c->planBS = 0;
+  c->streamPlanKey[0] = ~0ull;
+  const uint64_t stagedBytes = at + kPad;
+  hipError_t e = hipSuccess;
+  if (int r = reserve_all(c, stagedBytes)) return r;
+  if ((e = c->staged.reserve(stagedBytes)) || (e = c->batchItems.reserve(nb * sizeof(BatchItem) + 64)))
+    return c->fail(SZ4_E_NOMEM, "staging", e);
+  // the item table goes up with the plan, on the call's stream; `items` lives until the run has finished
+  if ((e = hipMemcpyAsync(c->batchItems.p, items.data(), nb * sizeof(BatchItem), hipMemcpyHostToDevice, s)))
+    return c->fail(SZ4_E_DEVICE, "upload items", e);
+  if (c->timing) hipEventRecord(c->evGather[0], s);
+  launch_batch_gather(c->batchItems.as<BatchItem>(), nb, c->staged.as<uint8_t>(), stagedBytes, s);
+  if (c->timing) hipEventRecord(c->evGather[1], s);
+  uint64_t size = 0;
+  if (int r = run_pipeline(c, maxChain, c->staged.as<uint8_t>(), nullptr, 0, false, out, outCap, &size, s)) return r;
+  if (c->timing) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->evGather[0], c->evGather[1]) == hipSuccess) c->gatherMs += ms;
+  }
+  bytes.resize(nb);
+  if ((e = hipMemcpy(bytes.data(), c->blockBytes.p, nb * 4ull, hipMemcpyDeviceToHost)))
+    return c->fail(SZ4_E_DEVICE, "block sizes", e);
+  return SZ4_OK;
+}
+
+// One piece: items [i0, i1) of the call.  At levels above 0 the items whose window fits the finders' LDS and
+// the items whose window does not are separate pipeline runs (finish_plan picks the finder per launch: one
+// large item would take every small one to the HBM finder).  A piece of one kind compresses straight to
+// its place in d_out; a mixed piece compresses both runs into batchTmp and k_batch_move puts every block at
+// its caller-order offset -- no payload byte passes through the host.  ext[i] receives item i's bytes in
+// d_out (0 for an empty item); the piece occupies d_out[pos, pos + sum of ext).
+int batch_piece(sz4_ctx* c, uint64_t i0, uint64_t i1, const void* const* ptrs, const uint32_t* sizes, uint32_t maxChain,
+                uint8_t* dOut, uint64_t pos, uint32_t* ext, float* stageSum, hipStream_t s)
+{
+  std::vector<uint64_t> run[2];
+  uint64_t bound[2] = {0, 0};
+  for (uint64_t i = i0; i < i1; i++) {
+    ext[i] = 0;
+    if (!sizes[i]) continue;
+    const int k = maxChain > 0 && !batch_fits_lds(sizes[i]) ? 1 : 0;
+    run[k].push_back(i);
+    bound[k] += (uint64_t)sizes[i] + 4;
+  }
+  auto add_stages = [&]() {
+    for (int k = 0; k < kStages; k++) stageSum[k] += c->stageMs[k];
+  };
+  std::vector<uint32_t> bytes[2];
+  if (run[0].empty() || run[1].empty()) {
+    const int k = run[0].empty() ? 1 : 0;
+    if (run[k].empty()) return SZ4_OK;
+    if (int r = batch_run(c, run[k], ptrs, sizes, maxChain, dOut + pos, bound[k], bytes[k], s)) return r;
+    add_stages();
+    for (size_t j = 0; j < run[k].size(); j++) ext[run[k][j]] = bytes[k][j] & 0x7FFFFFFFu;
+    return SZ4_OK;
+  }
+  hipError_t e;
+  if ((e = c->batchTmp.reserve(bound[0] + bound[1] + 64))) return c->fail(SZ4_E_NOMEM, "batch staging", e);
+  const uint64_t base[2] = {0, bound[0]};
+  for (int k = 0; k < 2; k++) {
+    if (int r = batch_run(c, run[k], ptrs, sizes, maxChain, c->batchTmp.as<uint8_t>() + base[k], bound[k], bytes[k], s))
+      return r;
+    add_stages();
+    for (size_t j = 0; j < run[k].size(); j++) ext[run[k][j]] = bytes[k][j] & 0x7FFFFFFFu;
+  }
+  // every block from its place in its run to its caller-order place, in entries of at most kBatchMoveMax bytes
+  std::vector<BatchMove> moves;
+  uint64_t from[2] = {base[0], base[1]}, to = pos;
+  size_t next[2] = {0, 0};
+  for (uint64_t i = i0; i < i1; i++) {
+    if (!ext[i]) continue;
+    const int k = next[0] < run[0].size() && run[0][next[0]] == i ? 0 : 1;
+    next[k]++;
+    for (uint64_t o = 0; o < ext[i]; o += kBatchMoveMax)
+      moves.push_back(BatchMove{from[k] + o, to + o, std::min<uint64_t>(kBatchMoveMax, ext[i] - o)});
+    from[k] += ext[i];
+    to += ext[i];
+  }
+  if ((e = c->batchMoves.reserve(moves.size() * sizeof(BatchMove) + 64))) return c->fail(SZ4_E_NOMEM, "batch moves", e);
+  if ((e = hipMemcpyAsync(c->batchMoves.p, moves.data(), moves.size() * sizeof(BatchMove), hipMemcpyHostToDevice, s)))
+    return c->fail(SZ4_E_DEVICE, "upload moves", e);
+  launch_batch_move(c->batchMoves.as<BatchMove>(), (uint32_t)moves.size(), c->batchTmp.as<uint8_t>(), dOut, s);
+  if ((e = hipGetLastError()) || (e = hipStreamSynchronize(s))) return c->fail(SZ4_E_DEVICE, "move blocks", e);
+  return SZ4_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1322,6 +1485,7 @@ int sz4_create(sz4_ctx** ctx, int device, uint64_t reserve_bytes)
     if (v >= (1u << 20)) c->streamChunk = v;
   }
   for (auto& e : c->ev) hipEventCreate(&e);
+  for (auto& e : c->evGather) hipEventCreate(&e);
   c->budget.bufs = c->all_buffers();
   for (DevBuf* b : c->budget.bufs) b->bud = &c->budget;
   c->budget.owner = c;
@@ -1347,6 +1511,8 @@ void sz4_destroy(sz4_ctx* c)
     for (hipEvent_t x : {c->evUp[k], c->evDone[k]})
       if (x) hipEventDestroy(x);
   for (auto& e : c->ev)
+    if (e) hipEventDestroy(e);
+  for (auto& e : c->evGather)
     if (e) hipEventDestroy(e);
   delete c;
 }
@@ -1468,16 +1634,7 @@ int sz4_compress_blocks_device(sz4_ctx* c, const void* d_in, uint64_t n, uint32_
   // most a quarter of the memory this context could use now (free + what it holds): a GPU shared with a
   // caching allocator gets smaller pieces instead of SZ4_E_NOMEM.  A piece whose reservation still fails is
   // halved and retried, down to kPieceFloor
-  uint64_t chunk = c->batchChunk;
-  if (c->budget.limit) {
-    chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(kPieceFloor, c->budget.limit / 64));
-  } else if (!c->batchChunkSet) {
-    size_t freeB = 0, totalB = 0;
-    if (hipMemGetInfo(&freeB, &totalB) == hipSuccess)
-      chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(kPieceFloor, (freeB + c->budget.used) / (4 * kScratchPerByte)));
-    else
-      (void)hipGetLastError();
-  }
+  const uint64_t chunk = piece_bytes(c);
   // equal pieces (the last one is not a small remainder): ceil(n / chunk) of them, whole blocks each
   const uint64_t nPieces = (n + chunk - 1) / std::max<uint64_t>(chunk, 1);
   const uint64_t even = (n + nPieces - 1) / nPieces;
@@ -1557,6 +1714,150 @@ int64_t sz4_last_block_sizes(sz4_ctx* c, uint32_t* sizes, uint64_t max_blocks)
   if (nb && hipMemcpy(sizes, c->blockBytes.p, nb * 4, hipMemcpyDeviceToHost) != hipSuccess) return SZ4_E_DEVICE;
   for (uint64_t i = 0; i < nb; i++) sizes[i] &= 0x7FFFFFFFu;
   return (int64_t)nb;
+}
+
+uint64_t sz4_batch_bound(const uint32_t* sizes, uint64_t count)
+{
+  uint64_t b = 0;
+  for (uint64_t i = 0; sizes && i < count; i++) b += (uint64_t)sizes[i] + 4;  // stored blocks are never larger than their input
+  return b;
+}
+
+int sz4_compress_batch_device(sz4_ctx* c, const void* const* in_ptrs, const uint32_t* in_sizes, uint64_t count,
+                              uint32_t max_chain, void* d_out, uint64_t out_cap, uint64_t* out_offsets, void* stream)
+{
+  if (!c || !out_offsets || (count && (!in_ptrs || !in_sizes)) || max_chain > 65535)
+    return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
+  c->begin_call();
+  for (uint64_t i = 0; i < count; i++) {
+    if (in_sizes[i] > kBlockMax) return c->fail(SZ4_E_ARG, "item larger than 4 MiB");
+    if (in_sizes[i] && !in_ptrs[i]) return c->fail(SZ4_E_ARG, "null item pointer");
+  }
+  // the kernels write the blocks in place: refuse a buffer that could be overrun
+  const uint64_t bound = sz4_batch_bound(in_sizes, count);
+  if (out_cap < bound) return c->fail(SZ4_E_CAPACITY, "out_cap < sz4_batch_bound(sizes, count)");
+  if (bound && !d_out) return c->fail(SZ4_E_ARG, "bad argument");
+  DeviceGuard guard(c->device);
+  try {
+  c->ghost = false;
+  c->dictBack = -1;
+  hipStream_t s = (hipStream_t)stream;
+  // per item sizes for sz4_last_block_sizes (0 for an empty item), filled piece by piece
+  c->hostBytes.assign(count, 0u);
+  c->batchChunked = true;
+  c->lastBlocks = 0;
+  c->gatherMs = 0;
+  float stageSum[kStages] = {};
+  // bounded memory: pieces of whole items in caller order, at most `piece` staged bytes and `cap` blocks each
+  // (an item larger than the piece is a piece on its own); a piece whose scratch cannot be reserved is
+  // halved and tried again, down to kPieceFloor, as in sz4_compress_blocks_device
+  uint64_t piece = piece_bytes(c);
+  uint64_t pos = 0;
+  out_offsets[0] = 0;
+  for (uint64_t i = 0; i < count;) {
+    const uint64_t cap = batch_block_cap(piece);
+    uint64_t j = i, staged = 0, blocks = 0;
+    for (; j < count; j++) {
+      if (!in_sizes[j]) continue;
+      const uint64_t st = batch_stride(in_sizes[j]);
+      if (blocks && (staged + st > piece || blocks >= cap)) break;
+      staged += st;
+      blocks++;
+    }
+    const int r = batch_piece(c, i, j, in_ptrs, in_sizes, max_chain, (uint8_t*)d_out, pos, c->hostBytes.data(), stageSum, s);
+    if (r == SZ4_E_NOMEM && blocks > 1 && piece > kPieceFloor) {
+      piece = std::max<uint64_t>(kPieceFloor, piece / 2);
+      continue;  // the same items again, in smaller pieces
+    }
+    if (r) return r;
+    for (; i < j; i++) {
+      pos += c->hostBytes[i];
+      out_offsets[i + 1] = pos;
+    }
+  }
+  if (c->timing)
+    for (int k = 0; k < kStages; k++) c->stageMs[k] = stageSum[k];
+  return SZ4_OK;
+  } catch (const std::bad_alloc&) {
+    return c->fail(SZ4_E_NOMEM, "host allocation");
+  }
+}
+
+float sz4_last_gather_ms(sz4_ctx* c) { return c ? c->gatherMs : 0.0f; }
+
+int sz4_unlz4_batch_device(sz4_ctx* c, const void* d_blocks, const uint64_t* offsets, uint64_t count, void* d_out,
+                           uint64_t out_cap, uint64_t* out_offsets, void* stream)
+{
+  if (!c || !out_offsets || (count && !offsets)) return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
+  c->begin_call();
+  DeviceGuard guard(c->device);
+  try {
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e;
+  c->unSplit = false;
+  c->unIndexParallel = false;
+  out_offsets[0] = 0;
+  // the extents of the non-empty items; an item shorter than its size word, or longer than any LZ4 block, is corrupt
+  std::vector<uint64_t> ext;
+  std::vector<uint64_t> item;
+  for (uint64_t i = 0; i < count; i++) {
+    if (offsets[i + 1] < offsets[i]) return c->fail(SZ4_E_CORRUPT, "offsets table decreases");
+    const uint64_t len = offsets[i + 1] - offsets[i];
+    if (!len) continue;
+    if (len < 4) return c->fail(SZ4_E_CORRUPT, "item shorter than its size word");
+    if (len - 4 > kMaxFrameBlock) return c->fail(SZ4_E_CORRUPT, "item larger than any LZ4 block");
+    ext.push_back(offsets[i]);
+    ext.push_back(offsets[i + 1]);
+    item.push_back(i);
+  }
+  if (item.size() >= (1ull << 31)) return c->fail(SZ4_E_ARG, "too many items");
+  const uint32_t nb = (uint32_t)item.size();
+  if (!nb) {
+    for (uint64_t i = 0; i < count; i++) out_offsets[i + 1] = 0;
+    return SZ4_OK;
+  }
+  if (!d_blocks) return c->fail(SZ4_E_ARG, "bad argument");
+  const uint8_t* f = (const uint8_t*)d_blocks;
+  const uint64_t n = offsets[count];  // every read of the passes below stays under it
+  if ((e = c->unBlk.reserve(nb * sizeof(UnBlock) + 64)) || (e = c->unBatch.reserve(ext.size() * 8 + 64)) ||
+      (e = c->unFlags.reserve(64)) || (e = c->unSeq.reserve(unlz4_seq_entries(n, nb) * sizeof(uint4) + 64)))
+    return c->fail(SZ4_E_NOMEM, "decoder scratch", e);
+  uint32_t* status = c->unFlags.as<uint32_t>();
+  uint32_t st = 0;
+  c->hUn.resize(nb);
+  if ((e = hipMemcpyAsync(c->unBatch.p, ext.data(), ext.size() * 8, hipMemcpyHostToDevice, s)) ||
+      (e = hipMemsetAsync(status, 0, 4, s)))
+    return c->fail(SZ4_E_DEVICE, "decoder plan", e);
+  launch_unlz4_batch_plan(f, c->unBatch.as<uint64_t>(), nb, c->unBlk.as<UnBlock>(), status, s);
+  launch_unlz4_sizes(f, n, c->unBlk.as<UnBlock>(), nb, c->unSeq.as<uint4>(), s);
+  if ((e = hipGetLastError()) || (e = hipMemcpyAsync(c->hUn.data(), c->unBlk.p, nb * sizeof(UnBlock), hipMemcpyDeviceToHost, s)) ||
+      (e = hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, s)) || (e = hipStreamSynchronize(s)))
+    return c->fail(SZ4_E_DEVICE, "block sizes", e);
+  if (st) return c->fail(SZ4_E_CORRUPT, "size word disagrees with the item's extent");
+  uint64_t w = 0;
+  uint64_t i = 0;
+  for (uint32_t b = 0; b < nb; b++) {
+    UnBlock& B = c->hUn[b];
+    if (B.size == kNone) return c->fail(SZ4_E_CORRUPT, "malformed LZ4 block");
+    for (; i <= item[b]; i++) out_offsets[i] = w;
+    B.dst = w;
+    w += B.size;
+  }
+  for (; i <= count; i++) out_offsets[i] = w;
+  if (w > out_cap || (w && !d_out)) return c->fail(SZ4_E_CAPACITY, "output buffer too small");
+  if (!w) return SZ4_OK;
+  if ((e = hipMemcpyAsync(c->unBlk.p, c->hUn.data(), nb * sizeof(UnBlock), hipMemcpyHostToDevice, s)) ||
+      (e = hipMemsetAsync(status, 0, 4, s)))
+    return c->fail(SZ4_E_DEVICE, "decoder plan", e);
+  launch_unlz4_blocks_indep(f, n, c->unBlk.as<UnBlock>(), nb, c->unSeq.as<uint4>(), (uint8_t*)d_out, status, s);
+  if ((e = hipGetLastError()) || (e = hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, s)) ||
+      (e = hipStreamSynchronize(s)))
+    return c->fail(SZ4_E_DEVICE, "decode", e);
+  if (st) return c->fail(SZ4_E_DEVICE, "decoded length differs from the size pass");
+  return SZ4_OK;
+  } catch (const std::bad_alloc&) {
+    return c->fail(SZ4_E_NOMEM, "host allocation");
+  }
 }
 
 int sz4_lz4_stream(sz4_ctx* c, sz4_get_bytes get_bytes, sz4_send_bytes send_bytes, uint32_t max_chain, const void* dict,

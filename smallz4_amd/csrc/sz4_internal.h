@@ -197,8 +197,8 @@ struct UnBlock {
 // Split mode (frames with large blocks): every block is cut into sub-segments of kUnSub payload bytes,
 // parsed speculatively from their first byte (k_unlz4_spec), joined to the true token chain per block
 // (k_unlz4_fix), decoded into a u32 value-or-reference image one wavefront per sub-segment
-// (k_unlz4_sub), whose references to earlier sub-segments are resolved by pointer jumping
-// (k_unlz4_resolve) before the bytes are packed (k_unlz4_pack).
+// (k_unlz4_sub); k_unlz4_pack then follows every reference to an earlier sub-segment down to its byte
+// while it packs the output, and reports the longest reference chain (hops) it followed.
 constexpr uint32_t kUnSub = 8192;
 constexpr uint32_t kUnSubCap = kUnSub / 3 + 4;    // sequences one walk over a sub-segment records
 constexpr uint32_t kUnSplitMin = 256u << 10;      // a block of at least this many payload bytes: split mode
@@ -233,6 +233,15 @@ void launch_unlz4_sizes(const uint8_t* f, uint64_t n, UnBlock* blk, uint32_t nb,
 // flags: nb done flags, then the status word, then the ticket (zeroed before the launch)
 void launch_unlz4_blocks(const uint8_t* f, uint64_t n, const UnBlock* blk, uint32_t nb, const uint4* seq, uint8_t* out,
                          const uint8_t* dict, uint64_t dl, uint32_t* flags, hipStream_t s);
+// independent mode (the batch decoder): every block decodes on its own -- a match source below the block's
+// first output byte reads 0 (the reference's zero-initialised history), never another block's output, and no
+// block waits for another.  flags: the status word alone (zeroed before the launch)
+void launch_unlz4_blocks_indep(const uint8_t* f, uint64_t n, const UnBlock* blk, uint32_t nb, const uint4* seq,
+                               uint8_t* out, uint32_t* flags, hipStream_t s);
+// batch decoder plan: block b is the bare LZ4 block f[ext[2b], ext[2b + 1]) (4-byte size word + payload, at
+// least 4 bytes); fills src / len / stored and sets *status when a size word disagrees with its extent
+void launch_unlz4_batch_plan(const uint8_t* f, const uint64_t* ext, uint32_t nb, UnBlock* blk, uint32_t* status,
+                             hipStream_t s);
 // split mode: seq holds 2 * kUnSubCap entries per sub-segment (re-parsed prefix, speculative list), masks
 // kUnAuxWords words per sub-segment (the token-start mask and k_unlz4_spec's side tables)
 void launch_unlz4_split_sizes(const uint8_t* f, uint64_t n, UnBlock* blk, uint32_t nb, UnSub* subs, uint32_t nsub,
@@ -241,5 +250,22 @@ void launch_unlz4_split_sizes(const uint8_t* f, uint64_t n, UnBlock* blk, uint32
 void launch_unlz4_split_decode(const uint8_t* f, uint64_t n, const UnBlock* blk, const UnSub* subs, uint32_t nsub,
                                const uint4* seq, uint32_t* image, const uint8_t* dict, uint64_t dl, hipStream_t s);
 void launch_unlz4_pack(uint32_t* image, uint64_t total, uint8_t* out, uint32_t* hops, hipStream_t s);
+
+// ragged batch API (sz4_batch.hip).  One item of a pipeline run: `size` bytes at device address `src` (any
+// alignment) are staged at [start, start + size); starts are multiples of kBatchAlign and ascending
+constexpr uint64_t kBatchAlign = 64;
+struct BatchItem {
+  uint64_t src, start, size;
+};
+// stages the items and zero-fills every other byte of staged[0, stagedBytes) (the gaps between items and the
+// pad after the last one); stagedBytes is a multiple of 16 and `staged` 16-byte aligned
+void launch_batch_gather(const BatchItem* items, uint32_t n, uint8_t* staged, uint64_t stagedBytes, hipStream_t s);
+// moves compressed blocks to their caller-order place: entry k copies len bytes from `from + src` to `to + dst`
+// (the host cuts long blocks into entries of at most kBatchMoveMax bytes, so the work is balanced by bytes)
+constexpr uint64_t kBatchMoveMax = 65536;
+struct BatchMove {
+  uint64_t src, dst, len;
+};
+void launch_batch_move(const BatchMove* moves, uint32_t n, const uint8_t* from, uint8_t* to, hipStream_t s);
 
 }  // namespace sz4

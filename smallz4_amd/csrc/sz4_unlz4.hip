@@ -706,6 +706,10 @@ __device__ uint64_t unlz4_walk_v(const uint8_t* __restrict__ f, uint64_t n, cons
 // Replays block bi's sequence list into `out` (and the ring); returns the decoded length.
 // From sequence b0Start on, with wStart bytes of the block already decoded (and drained): how the vector
 // decoder below hands a block over when a match reads below the block start.
+// kIndep (the batch decoder's bare blocks): the block decodes on its own.  Nothing precedes it, so a match
+// source below B.dst reads 0 -- the reference's zero-initialised history -- and neither another block's
+// output nor its done flag is ever read (blk, done, dict are unused).
+template <bool kIndep>
 __device__ uint64_t unlz4_decode(const uint8_t* __restrict__ f, uint64_t n, const UnBlock& B, uint32_t bi, uint32_t lane,
                                  const uint4* __restrict__ seq, uint8_t* __restrict__ out, uint8_t* __restrict__ ring,
                                  const uint8_t* __restrict__ dict, uint64_t dl, const UnBlock* __restrict__ blk,
@@ -775,7 +779,7 @@ __device__ uint64_t unlz4_decode(const uint8_t* __restrict__ f, uint64_t n, cons
       if (M) {
         const uint64_t Q = P + L;                     // the match's first output byte
         const int64_t lo = (int64_t)Q - (int64_t)off;  // lowest byte it reads
-        if (lo < (int64_t)floorPos && floorPos > 0 && waitIdx > 0) {
+        if (!kIndep && lo < (int64_t)floorPos && floorPos > 0 && waitIdx > 0) {
           // the blocks holding output in [max(lo, 0), floorPos) must be finished
           while (waitIdx > 0 && (int64_t)floorPos > lo && floorPos > 0) {
             waitIdx--;
@@ -813,6 +817,7 @@ __device__ uint64_t unlz4_decode(const uint8_t* __restrict__ f, uint64_t n, cons
           uint8_t v = 0;
           if (jj < M) {
             if (s >= (int64_t)B.dst && s >= ringLo) v = ring[(uint64_t)s & (kRing - 1u)];
+            else if (kIndep) v = s >= (int64_t)B.dst ? out[s] : (uint8_t)0;  // drained output of this block, or 0
             else if (s >= 0) v = out[s];  // drained output of this block, or an earlier (finished) block
             else if ((uint64_t)(-s) <= dl) v = dict[dl - (uint64_t)(-s)];  // the dictionary's tail
             // else 0: before the history (oz_unlz4's zero-initialised history)
@@ -849,7 +854,9 @@ __device__ __forceinline__ uint32_t un_scan_max(uint32_t v)
 // earlier lane of the window otherwise (resolved by pointer jumping: src -> src - offset until a known
 // byte, at most log2(64) rounds per distinct offset).  Blocks whose matches stay inside the block
 // (independent blocks: every frame bench.py decodes); the first batch with a match reaching below the
-// block start (linked blocks, a dictionary) or an empty sequence continues in unlz4_decode.
+// block start (linked blocks, a dictionary) or an empty sequence continues in unlz4_decode (kIndep: in its
+// independent mode).
+template <bool kIndep>
 __device__ uint64_t unlz4_decode_vec(const uint8_t* __restrict__ f, uint64_t n, const UnBlock& B, uint32_t bi,
                                      uint32_t lane, const uint4* __restrict__ seq, uint8_t* __restrict__ out,
                                      uint8_t* __restrict__ ring, uint32_t* __restrict__ slot,
@@ -875,7 +882,7 @@ __device__ uint64_t unlz4_decode_vec(const uint8_t* __restrict__ f, uint64_t n, 
     if (__ballot(far || (lane < cnt && tot == 0u))) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      return unlz4_decode(f, n, B, bi, lane, seq, out, ring, dict, dl, blk, done, status, b0, w);
+      return unlz4_decode<kIndep>(f, n, B, bi, lane, seq, out, ring, dict, dl, blk, done, status, b0, w);
     }
     uint32_t jc = 0;  // 1 + the sequence covering the byte before the window
     for (uint32_t W = 0; W < blen; W += 64) {
@@ -1349,7 +1356,10 @@ __global__ __launch_bounds__(64) void k_unlz4_sizes(const uint8_t* __restrict__ 
   }
 }
 
-// flags[0..nb) done flags, flags[nb] status bits, flags[nb + 1] ticket (all zeroed before the launch)
+// flags[0..nb) done flags, flags[nb] status bits, flags[nb + 1] ticket (all zeroed before the launch).
+// kIndep (bare blocks of the batch decoder, no block reads another's output): block blockIdx.x, no claim
+// order, no done flags; flags is the status word alone
+template <bool kIndep>
 __global__ __launch_bounds__(64) void k_unlz4_blocks(const uint8_t* __restrict__ f, uint64_t n, const UnBlock* __restrict__ blk,
                                                      uint32_t nb, const uint4* __restrict__ seqAll, uint8_t* __restrict__ out,
                                                      const uint8_t* __restrict__ dict, uint64_t dl, uint32_t* __restrict__ flags)
@@ -1357,18 +1367,19 @@ __global__ __launch_bounds__(64) void k_unlz4_blocks(const uint8_t* __restrict__
   __shared__ uint8_t ring[kRing];
   const uint32_t lane = threadIdx.x;
   uint32_t* done = flags;
-  uint32_t* status = flags + nb;
+  uint32_t* status = kIndep ? flags : flags + nb;
   // blocks are claimed in order by running workgroups: every block a claim can wait for has been
   // claimed by a workgroup that is already running (no dispatch-order assumption)
-  uint32_t t = 0;
-  if (lane == 0) t = atomicAdd(&flags[nb + 1], 1u);
+  uint32_t t = blockIdx.x;
+  if (!kIndep && lane == 0) t = atomicAdd(&flags[nb + 1], 1u);
   const uint32_t bi = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
   if (bi >= nb) return;
   const UnBlock B = blk[bi];
   __shared__ uint32_t slot[64];
-  const uint64_t got = unlz4_decode_vec(f, n, B, bi, lane, seq_base(const_cast<uint4*>(seqAll), B, bi), out, ring, slot,
-                                        dict, dl, blk, done, status);
+  const uint64_t got = unlz4_decode_vec<kIndep>(f, n, B, bi, lane, seq_base(const_cast<uint4*>(seqAll), B, bi), out, ring,
+                                                slot, dict, dl, blk, done, status);
   if (lane == 0 && got != B.size) atomicOr(status, 1u);
+  if (kIndep) return;
   // publish: this wave's stores drained, written back (agent release), then the flag
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -1822,7 +1833,41 @@ void launch_unlz4_sizes(const uint8_t* f, uint64_t n, UnBlock* blk, uint32_t nb,
 void launch_unlz4_blocks(const uint8_t* f, uint64_t n, const UnBlock* blk, uint32_t nb, const uint4* seq, uint8_t* out,
                          const uint8_t* dict, uint64_t dl, uint32_t* flags, hipStream_t s)
 {
-  if (nb) hipLaunchKernelGGL(k_unlz4_blocks, dim3(nb), dim3(64), 0, s, f, n, blk, nb, seq, out, dict, dl, flags);
+  if (nb) hipLaunchKernelGGL(k_unlz4_blocks<false>, dim3(nb), dim3(64), 0, s, f, n, blk, nb, seq, out, dict, dl, flags);
+}
+
+void launch_unlz4_blocks_indep(const uint8_t* f, uint64_t n, const UnBlock* blk, uint32_t nb, const uint4* seq,
+                               uint8_t* out, uint32_t* flags, hipStream_t s)
+{
+  if (nb)
+    hipLaunchKernelGGL(k_unlz4_blocks<true>, dim3(nb), dim3(64), 0, s, f, n, blk, nb, seq, out, (const uint8_t*)nullptr,
+                       (uint64_t)0, flags);
+}
+
+// Batch decoder plan: the UnBlock records straight from the items' extents -- there is no frame to index.
+// An item's size word (low 31 bits) must be its extent less the word itself; the record keeps the extent's
+// length either way, so the sizes pass stays inside the item.  An item that is a zero word alone is what
+// the reference reads as the end mark: it decodes to nothing (marked stored, 0 bytes).
+__global__ __launch_bounds__(256) void k_unlz4_batch_plan(const uint8_t* __restrict__ f, const uint64_t* __restrict__ ext,
+                                                          uint32_t nb, UnBlock* __restrict__ blk,
+                                                          uint32_t* __restrict__ status)
+{
+  const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= nb) return;
+  const uint64_t at = ext[2 * b], len = ext[2 * b + 1] - at - 4;
+  const uint32_t word = (uint32_t)f[at] | ((uint32_t)f[at + 1] << 8) | ((uint32_t)f[at + 2] << 16) | ((uint32_t)f[at + 3] << 24);
+  if ((uint64_t)(word & 0x7FFFFFFFu) != len) atomicOr(status, 1u);
+  UnBlock B{};
+  B.src = at + 4;
+  B.len = (uint32_t)len;
+  B.stored = (word >> 31) | (len == 0 ? 1u : 0u);
+  blk[b] = B;
+}
+
+void launch_unlz4_batch_plan(const uint8_t* f, const uint64_t* ext, uint32_t nb, UnBlock* blk, uint32_t* status,
+                             hipStream_t s)
+{
+  if (nb) hipLaunchKernelGGL(k_unlz4_batch_plan, dim3((nb + 255) / 256), dim3(256), 0, s, f, ext, nb, blk, status);
 }
 
 }  // namespace sz4
