@@ -129,6 +129,37 @@ float sz4_last_gather_ms(sz4_ctx* ctx);
 int sz4_unlz4_batch_device(sz4_ctx* ctx, const void* d_blocks, const uint64_t* offsets, uint64_t count,
                            void* d_out, uint64_t out_cap, uint64_t* out_offsets, void* stream);
 
+/* ---- typed items: the byte-plane split (Parquet's BYTE_STREAM_SPLIT, Blosc's and HDF5's "shuffle") ----
+ * An item of n bytes holding elements of width E (1, 2, 4 or 8) has m = n / E whole elements and n % E tail
+ * bytes; its split is
+ *     split[k * m + e] = item[e * E + k]   (0 <= k < E, 0 <= e < m)
+ *     split[E * m + j] = item[E * m + j]   (the tail, unchanged, after the planes)
+ * (the identity for E = 1 and for n < E).  smallz4_amd/planes.py states both directions in numpy.
+ *
+ * As sz4_compress_batch_device; item i is split by elem_sizes[i] (HOST array of count, each 1, 2, 4 or 8;
+ * anything else: SZ4_E_ARG before any work) while it is staged, at no extra pass over the data.  Item i's
+ * output is exactly what smallz4::lz4 emits for split(item i) on its own: an ordinary LZ4 block that any
+ * decoder reads, giving the split bytes.  Widths are per item; with all widths 1 the call is the plain call.
+ * sz4_batch_bound, out_offsets, sz4_last_block_sizes and the pieces are unchanged, and sz4_last_gather_ms
+ * covers the splitting gather. */
+int sz4_compress_batch_typed_device(sz4_ctx* ctx, const void* const* in_ptrs, const uint32_t* in_sizes,
+                                    const uint8_t* elem_sizes, uint64_t count, uint32_t max_chain, void* d_out,
+                                    uint64_t out_cap, uint64_t* out_offsets, void* stream);
+
+/* As sz4_unlz4_batch_device; item i's decoded bytes are merged (the inverse of the split) by elem_sizes[i]
+ * on their way to d_out, so d_out[out_offsets[i], out_offsets[i + 1]) is the original item.  d_out may have
+ * any alignment; an item that lands at a multiple of its element width is merged with 16-byte stores and
+ * byte permutes, any other byte by byte.  The blocks decode into a buffer of the context (the decoded
+ * bytes once more, counted by sz4_device_bytes, released by sz4_trim).  Same query mode, same error codes;
+ * a width other than 1, 2, 4 or 8: SZ4_E_ARG before any work. */
+int sz4_unlz4_batch_typed_device(sz4_ctx* ctx, const void* d_blocks, const uint64_t* offsets,
+                                 const uint8_t* elem_sizes, uint64_t count, void* d_out, uint64_t out_cap,
+                                 uint64_t* out_offsets, void* stream);
+
+/* Device time (milliseconds) of the merge kernel of the last sz4_unlz4_batch_typed_device call (with
+ * sz4_set_timing on; 0 when every width was 1). */
+float sz4_last_merge_ms(sz4_ctx* ctx);
+
 /* Whole-stream compression with the exact semantics of
  * smallz4::lz4(getBytes, sendBytes, maxChainLength, dictionary, useLegacyFormat)
  * (reference smallz4.h:47-64): 4 MiB dependent blocks (8 MiB independent

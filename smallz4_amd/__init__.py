@@ -12,6 +12,9 @@ plus the data-parallel entry point the GPU is built for:
         -> frame whose every block equals smallz4's output for that block alone
     Compressor().compress_batch(items, max_chain_length=65535) / unlz4_batch(blocks)
         -> many separate buffers of different sizes, one independently decodable LZ4 block each
+    Compressor().compress_batch_typed(items, elem_sizes) / unlz4_batch_typed(blocks, elem_sizes)
+    Compressor().compress_tensor(t) / decompress_tensor(ct)
+        -> the same for items of fixed-width elements, split into byte planes (planes.py) on the way
 
 All compression runs in the HIP library smallz4_amd/lib/libsmallz4_amd.so; there
 is no CPU fallback.
@@ -19,6 +22,7 @@ is no CPU fallback.
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 
 from . import _native
 
@@ -42,6 +46,20 @@ def level_to_chain(level: int) -> int:
     if not 0 <= level <= 9:
         raise ValueError("level must be 0..9")
     return 65535 if level == 9 else level
+
+
+@dataclasses.dataclass
+class CompressedTensor:
+    """What compress_tensor returns: typed blocks on the device (no serialised format)."""
+    blocks: object       # device uint8 tensor: the bare LZ4 blocks, back to back
+    offsets: list        # chunk i is blocks[offsets[i]:offsets[i + 1]]
+    dtype: object        # the tensor's torch dtype (its element size is every chunk's width)
+    shape: tuple
+    chunk_bytes: int     # bytes of the tensor per chunk (the last chunk holds the rest)
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.offsets[-1])
 
 
 class Compressor:
@@ -272,6 +290,135 @@ class Compressor:
         """Device time of the last compress_batch_device call's gather kernels (with set_timing on)."""
         return float(self._lib.sz4_last_gather_ms(self._h))
 
+    # -- typed ragged batch: items of fixed-width elements, split into byte planes (planes.py) ------
+    def compress_batch_typed_device(self, ptrs, sizes, elems, d_out: int, out_cap: int,
+                                    max_chain_length: int = MaxChainLength, stream: int = 0) -> list[int]:
+        """compress_batch_device with item i split by its element width elems[i] (1, 2, 4 or 8) while it is
+        staged: block i is oz_block(planes.split(item i, elems[i])) (see sz4_compress_batch_typed_device)."""
+        count = len(sizes)
+        if len(ptrs) != count or len(elems) != count:
+            raise ValueError("ptrs, sizes and elems differ in length")
+        p = (ctypes.c_void_p * max(count, 1))(*[int(x) or None for x in ptrs])
+        z = (ctypes.c_uint32 * max(count, 1))(*[int(x) for x in sizes])
+        w = (ctypes.c_uint8 * max(count, 1))(*[int(x) & 0xFF if 0 <= int(x) < 256 else 0 for x in elems])
+        off = (ctypes.c_uint64 * (count + 1))()
+        rc = self._lib.sz4_compress_batch_typed_device(self._h, p, z, w, count, int(max_chain_length),
+                                                       ctypes.c_void_p(d_out), out_cap, off, ctypes.c_void_p(stream))
+        self._check(rc, "sz4_compress_batch_typed_device")
+        return list(off)
+
+    def unlz4_batch_typed_device(self, d_blocks: int, offsets, elems, d_out: int, out_cap: int,
+                                 stream: int = 0) -> list[int]:
+        """unlz4_batch_device with item i merged by elems[i] on its way to d_out, which then holds the
+        original items (see sz4_unlz4_batch_typed_device).  d_out = 0, out_cap = 0 queries the offsets."""
+        count = len(offsets) - 1
+        if count < 0:
+            raise ValueError("offsets needs count + 1 entries")
+        if len(elems) != count:
+            raise ValueError("offsets and elems differ in length")
+        o = (ctypes.c_uint64 * (count + 1))(*[int(x) for x in offsets])
+        w = (ctypes.c_uint8 * max(count, 1))(*[int(x) & 0xFF if 0 <= int(x) < 256 else 0 for x in elems])
+        res = (ctypes.c_uint64 * (count + 1))()
+        rc = self._lib.sz4_unlz4_batch_typed_device(self._h, ctypes.c_void_p(d_blocks), o, w, count, ctypes.c_void_p(d_out),
+                                                    out_cap, res, ctypes.c_void_p(stream))
+        if not (rc == _native.SZ4_E_CAPACITY and not d_out and not out_cap):
+            self._check(rc, "sz4_unlz4_batch_typed_device")
+        return list(res)
+
+    def compress_batch_typed(self, items, elem_sizes=None, max_chain_length: int = MaxChainLength) -> list[bytes]:
+        """compress_batch for typed items: [oz_block(planes.split(item, E)) for item in items].  A torch tensor
+        of any dtype is taken as its bytes with E = its element size (1, 2, 4 or 8; any other: TypeError);
+        a bytes-like needs its width in elem_sizes (one entry per item; None for a tensor = its dtype's)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if elem_sizes is not None and len(elem_sizes) != len(items):
+            raise ValueError("items and elem_sizes differ in length")
+        views, elems = [], []
+        for i, it in enumerate(items):
+            e = elem_sizes[i] if elem_sizes is not None else None
+            if isinstance(it, torch.Tensor):
+                e = it.element_size() if e is None else e
+                t = it.to(dev).contiguous().reshape(-1).view(torch.uint8)
+            else:
+                if e is None:
+                    raise TypeError("a bytes-like item needs its element width in elem_sizes")
+                m = memoryview(it).cast("B")
+                t = (torch.frombuffer(bytearray(m), dtype=torch.uint8).to(dev) if len(m)
+                     else torch.empty(0, dtype=torch.uint8, device=dev))
+            if e not in (1, 2, 4, 8):
+                raise TypeError(f"element width {e} is not 1, 2, 4 or 8")
+            views.append(t)
+            elems.append(e)
+        sizes = [v.numel() for v in views]
+        cap = self.batch_bound(sizes)
+        out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        off = self.compress_batch_typed_device([v.data_ptr() if n else 0 for v, n in zip(views, sizes)], sizes, elems,
+                                               out.data_ptr(), cap, max_chain_length, stream)
+        raw = out[:off[-1]].cpu().numpy().tobytes()
+        return [raw[off[i]:off[i + 1]] for i in range(len(sizes))]
+
+    def unlz4_batch_typed(self, blocks, elem_sizes) -> list[bytes]:
+        """The reverse of compress_batch_typed: every bare block decoded on its own and merged by its width."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        blocks = [bytes(b) for b in blocks]
+        offsets = [0]
+        for b in blocks:
+            offsets.append(offsets[-1] + len(b))
+        joined = bytearray().join(blocks)
+        d = (torch.frombuffer(joined, dtype=torch.uint8).to(dev) if joined
+             else torch.empty(16, dtype=torch.uint8, device=dev))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        sizes = self.unlz4_batch_typed_device(d.data_ptr(), offsets, elem_sizes, 0, 0, stream)
+        out = torch.empty(max(sizes[-1], 16), dtype=torch.uint8, device=dev)
+        off = self.unlz4_batch_typed_device(d.data_ptr(), offsets, elem_sizes, out.data_ptr(), sizes[-1], stream)
+        raw = out[:off[-1]].cpu().numpy().tobytes()
+        return [raw[off[i]:off[i + 1]] for i in range(len(blocks))]
+
+    def compress_tensor(self, t, chunk_bytes: int = 65536, max_chain_length: int = MaxChainLength) -> "CompressedTensor":
+        """A tensor as typed blocks of chunk_bytes each (the last one shorter), all of width t.element_size().
+        The tensor is made contiguous and cut by pointer: its payload is not copied, and the blocks stay on
+        the device -- only their offsets come to the host."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        e = t.element_size()
+        if e not in (1, 2, 4, 8):
+            raise TypeError(f"element width {e} is not 1, 2, 4 or 8")
+        if not 0 < chunk_bytes <= 4 << 20 or chunk_bytes % e:
+            raise ValueError("chunk_bytes must be a multiple of the element size, at most 4 MiB")
+        flat = t.detach().to(dev).contiguous().reshape(-1).view(torch.uint8)
+        n = flat.numel()
+        sizes = [min(chunk_bytes, n - o) for o in range(0, n, chunk_bytes)]
+        base = flat.data_ptr()
+        cap = self.batch_bound(sizes)
+        out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        off = self.compress_batch_typed_device([base + k * chunk_bytes for k in range(len(sizes))], sizes,
+                                               [e] * len(sizes), out.data_ptr(), cap, max_chain_length, stream)
+        return CompressedTensor(out[:off[-1]].clone(), off, t.dtype, tuple(t.shape), chunk_bytes)
+
+    def decompress_tensor(self, ct: "CompressedTensor"):
+        """The tensor compress_tensor took, on the device, in its dtype and shape."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        e = torch.empty(0, dtype=ct.dtype).element_size()
+        n = e
+        for d in ct.shape:
+            n *= d
+        blocks = ct.blocks.to(dev)
+        out = torch.empty(n, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        off = self.unlz4_batch_typed_device(blocks.data_ptr(), ct.offsets, [e] * (len(ct.offsets) - 1), out.data_ptr(), n,
+                                            stream)
+        if off[-1] != n:
+            raise _native.NativeError(f"the blocks decode to {off[-1]} bytes, the tensor has {n}")
+        return out.view(ct.dtype).reshape(ct.shape)
+
+    def last_merge_ms(self) -> float:
+        """Device time of the last unlz4_batch_typed_device call's merge kernel (with set_timing on)."""
+        return float(self._lib.sz4_last_merge_ms(self._h))
+
     # -- decoder: the reference's smallz4cat -----------------------------------------------------
     def unlz4(self, frame: bytes, dictionary: bytes = b"") -> bytes:
         """smallz4cat's unlz4 (smallz4cat.c:112-360) on the GPU: the bytes `frame` decodes to.
@@ -412,3 +559,23 @@ def compress_batch(items, max_chain_length: int = MaxChainLength) -> list[bytes]
 def unlz4_batch(blocks) -> list[bytes]:
     """Every bare block decoded on its own (Compressor.unlz4_batch)."""
     return _ctx().unlz4_batch(blocks)
+
+
+def compress_batch_typed(items, elem_sizes=None, max_chain_length: int = MaxChainLength) -> list[bytes]:
+    """Every item split into its byte planes and compressed as one LZ4 block (Compressor.compress_batch_typed)."""
+    return _ctx().compress_batch_typed(items, elem_sizes, max_chain_length)
+
+
+def unlz4_batch_typed(blocks, elem_sizes) -> list[bytes]:
+    """Every bare block decoded on its own and merged by its width (Compressor.unlz4_batch_typed)."""
+    return _ctx().unlz4_batch_typed(blocks, elem_sizes)
+
+
+def compress_tensor(t, chunk_bytes: int = 65536, max_chain_length: int = MaxChainLength) -> CompressedTensor:
+    """A tensor as typed blocks on the device (Compressor.compress_tensor)."""
+    return _ctx().compress_tensor(t, chunk_bytes, max_chain_length)
+
+
+def decompress_tensor(ct: CompressedTensor):
+    """The tensor compress_tensor took, on the device (Compressor.decompress_tensor)."""
+    return _ctx().decompress_tensor(ct)

@@ -41,6 +41,12 @@ SIGNATURES = {
                                          ctypes.POINTER(_u64), _vp]),
     "sz4_last_gather_ms": (ctypes.c_float, [_vp]),
     "sz4_unlz4_batch_device": (_i32, [_vp, _vp, ctypes.POINTER(_u64), _u64, _vp, _u64, ctypes.POINTER(_u64), _vp]),
+    "sz4_compress_batch_typed_device": (_i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_u32),
+                                               ctypes.POINTER(ctypes.c_uint8), _u64, _u32, _vp, _u64,
+                                               ctypes.POINTER(_u64), _vp]),
+    "sz4_unlz4_batch_typed_device": (_i32, [_vp, _vp, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_uint8), _u64, _vp,
+                                            _u64, ctypes.POINTER(_u64), _vp]),
+    "sz4_last_merge_ms": (ctypes.c_float, [_vp]),
     "sz4_lz4": (_i32, [_vp, _vp, _u64, _u32, _vp, _u64, _i32, _vp, _u64, ctypes.POINTER(_u64)]),
     "sz4_lz4_bound": (_u64, [_u64, _i32]),
     "sz4_lz4_stream": (_i32, [_vp, GET_BYTES, SEND_BYTES, _u32, _vp, _u64, _i32, _vp]),

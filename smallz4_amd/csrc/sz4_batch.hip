@@ -1,8 +1,11 @@
 // sz4_batch.hip -- device pieces of the ragged batch API (sz4_compress_batch_device) for gfx950:
 //   k_batch_gather  stages many separately allocated buffers into the context's padded staging buffer
+//   k_batch_gather_planes  the same with the byte-plane split of typed items folded in
+//                   (sz4_compress_batch_typed_device: byte k of every element of an item stored together)
 //   k_batch_move    moves compressed blocks to their caller-order place when one piece ran as two
 //                   pipeline runs (items whose window fits the finders' LDS, and items whose does not)
-// Both are plain copies, bound by memory: 16-byte accesses on the aligned side, work cut by bytes.
+//   k_batch_merge   the inverse of the split, after the batch decoder (sz4_unlz4_batch_typed_device)
+// All are copies, bound by memory: 16-byte accesses on the aligned side, work cut by bytes.
 #include <hip/hip_runtime.h>
 
 #include "sz4_internal.h"
@@ -15,7 +18,8 @@ constexpr uint32_t kGatherTile = 1024;  // 16-byte staging words per workgroup s
 constexpr uint32_t kGatherGrid = 2048;  // workgroups at most (256 CUs x 8); the rest is a grid-stride loop
 
 // index of the last item in [lo, hi) whose start is <= pos (items[lo].start <= pos)
-__device__ __forceinline__ uint32_t item_at(const BatchItem* __restrict__ items, uint32_t lo, uint32_t hi, uint64_t pos)
+template <typename Item>
+__device__ __forceinline__ uint32_t item_at(const Item* __restrict__ items, uint32_t lo, uint32_t hi, uint64_t pos)
 {
   while (hi - lo > 1) {
     const uint32_t mid = lo + (hi - lo) / 2;
@@ -23,6 +27,35 @@ __device__ __forceinline__ uint32_t item_at(const BatchItem* __restrict__ items,
     else hi = mid;
   }
   return lo;
+}
+
+// bytes [o, o + 16) of the item at `src` (o < size; bytes from the item's end on read 0), from the one or two
+// aligned 16-byte source words that hold them
+__device__ __forceinline__ void gather_word(uint64_t src, uint64_t size, uint64_t o, uint64_t& r0, uint64_t& r1)
+{
+  const uint64_t p = src + o;
+  const uint32_t a = (uint32_t)(p & 15u);
+  const uint4* q = reinterpret_cast<const uint4*>(p - a);
+  const uint4 lo = q[0];
+  uint4 hi = make_uint4(0u, 0u, 0u, 0u);
+  if (a && p - a + 16 < src + size) hi = q[1];
+  const uint64_t x0 = lo.x | ((uint64_t)lo.y << 32), x1 = lo.z | ((uint64_t)lo.w << 32);
+  const uint64_t x2 = hi.x | ((uint64_t)hi.y << 32), x3 = hi.z | ((uint64_t)hi.w << 32);
+  // bytes [a, a + 16) of the 32 bytes x0..x3
+  const bool up = a >= 8;
+  const uint64_t s0 = up ? x1 : x0, s1 = up ? x2 : x1, s2 = up ? x3 : x2;
+  const uint32_t sh = (a & 7u) * 8u;
+  r0 = sh ? (s0 >> sh) | (s1 << (64u - sh)) : s0;
+  r1 = sh ? (s1 >> sh) | (s2 << (64u - sh)) : s1;
+  const uint64_t left = size - o;  // bytes of the item from this word on
+  if (left < 16) {
+    if (left <= 8) {
+      r1 = 0;
+      if (left < 8) r0 &= (1ull << (8 * left)) - 1;
+    } else {
+      r1 &= (1ull << (8 * (left - 8))) - 1;
+    }
+  }
 }
 
 // Every thread writes whole 16-byte words of the staging buffer; a word belongs to the last item that starts
@@ -48,31 +81,7 @@ __global__ __launch_bounds__(kGatherThreads) void k_batch_gather(const BatchItem
       const BatchItem it = items[item_at(items, first, last + 1, 16 * w)];
       const uint64_t o = 16 * w - it.start;  // item-relative offset of the word
       uint64_t r0 = 0, r1 = 0;
-      if (o < it.size) {
-        const uint64_t p = it.src + o;
-        const uint32_t a = (uint32_t)(p & 15u);
-        const uint4* q = reinterpret_cast<const uint4*>(p - a);
-        const uint4 lo = q[0];
-        uint4 hi = make_uint4(0u, 0u, 0u, 0u);
-        if (a && p - a + 16 < it.src + it.size) hi = q[1];
-        const uint64_t x0 = lo.x | ((uint64_t)lo.y << 32), x1 = lo.z | ((uint64_t)lo.w << 32);
-        const uint64_t x2 = hi.x | ((uint64_t)hi.y << 32), x3 = hi.z | ((uint64_t)hi.w << 32);
-        // bytes [a, a + 16) of the 32 bytes x0..x3
-        const bool up = a >= 8;
-        const uint64_t s0 = up ? x1 : x0, s1 = up ? x2 : x1, s2 = up ? x3 : x2;
-        const uint32_t sh = (a & 7u) * 8u;
-        r0 = sh ? (s0 >> sh) | (s1 << (64u - sh)) : s0;
-        r1 = sh ? (s1 >> sh) | (s2 << (64u - sh)) : s1;
-        const uint64_t left = it.size - o;  // bytes of the item from this word on
-        if (left < 16) {
-          if (left <= 8) {
-            r1 = 0;
-            if (left < 8) r0 &= (1ull << (8 * left)) - 1;
-          } else {
-            r1 &= (1ull << (8 * (left - 8))) - 1;
-          }
-        }
-      }
+      if (o < it.size) gather_word(it.src, it.size, o, r0, r1);
       *reinterpret_cast<uint4*>(staged + 16 * w) =
           make_uint4((uint32_t)r0, (uint32_t)(r0 >> 32), (uint32_t)r1, (uint32_t)(r1 >> 32));
     }
@@ -103,6 +112,226 @@ __global__ __launch_bounds__(256) void k_batch_move(const BatchMove* __restrict_
   for (uint64_t k = head + 16 * body + threadIdx.x; k < m.len; k += 256) dst[k] = src[k];
 }
 
+// ---- typed items: the byte-plane split and its inverse -----------------------------------------------
+// An item of `size` bytes and element width E (2, 4 or 8) has m = size / E whole elements: byte k of element
+// e is split byte k * m + e, and the size % E tail bytes follow the planes unchanged.
+struct __attribute__((packed)) Unaligned8 {
+  uint32_t x, y;
+};
+struct __attribute__((packed)) Unaligned4 {
+  uint32_t x;
+};
+struct __attribute__((packed)) Unaligned2 {
+  uint16_t x;
+};
+
+// v_perm_b32: result byte i is byte sel[i] of the 8 bytes {hi, lo} (0..3 = lo, 4..7 = hi, 0x0c = zero)
+__device__ __forceinline__ uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
+
+// byte k (0..3) of each of four words
+__device__ __forceinline__ uint32_t pick4(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, uint32_t k)
+{
+  const uint32_t sel = 0x0c0c0400u + k * 0x0101u;
+  return perm(perm(d3, d2, sel), perm(d1, d0, sel), 0x05040100u);
+}
+
+// 16 bytes of plane k: byte k of the 16 consecutive elements at p (16 * E source bytes, all inside the item,
+// so the loads may be unaligned and still touch nothing outside it)
+template <int E>
+__device__ __forceinline__ uint4 plane_word(const uint8_t* __restrict__ p, uint32_t k)
+{
+  uint32_t d[4 * E], r[4];
+#pragma unroll
+  for (int i = 0; i < E; i++) {
+    const Unaligned16 v = *reinterpret_cast<const Unaligned16*>(p + 16 * i);
+    d[4 * i] = v.x, d[4 * i + 1] = v.y, d[4 * i + 2] = v.z, d[4 * i + 3] = v.w;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    if (E == 2) {
+      r[j] = perm(d[2 * j + 1], d[2 * j], 0x06040200u + k * 0x01010101u);
+    } else if (E == 4) {
+      r[j] = pick4(d[4 * j], d[4 * j + 1], d[4 * j + 2], d[4 * j + 3], k);
+    } else {
+      const bool h = k >= 4;  // the element's upper word
+      r[j] = pick4(h ? d[8 * j + 1] : d[8 * j], h ? d[8 * j + 3] : d[8 * j + 2], h ? d[8 * j + 5] : d[8 * j + 4],
+                   h ? d[8 * j + 7] : d[8 * j + 6], k & 3u);
+    }
+  }
+  return make_uint4(r[0], r[1], r[2], r[3]);
+}
+
+// split bytes [o, o + 16) of an item byte by byte (a word that straddles two planes, the tail or the item's
+// end; bytes from the end on read 0): one division for the first byte, then the position is stepped
+__device__ __forceinline__ uint4 plane_bytes(const uint8_t* __restrict__ src, uint32_t size, uint32_t E, uint32_t m, uint32_t o)
+{
+  const uint32_t planes = m * E;
+  uint32_t k = 0, e = 0;
+  if (o < planes) {
+    k = o / m;
+    e = o - k * m;
+  }
+  uint64_t r[2] = {0, 0};
+#pragma unroll
+  for (uint32_t i = 0; i < 16; i++) {
+    const uint32_t pos = o + i;
+    if (pos < size) {
+      uint32_t at = pos;  // the tail lies where it lay
+      if (pos < planes) {
+        at = e * E + k;
+        if (++e == m) e = 0, k++;
+      }
+      r[i / 8] |= (uint64_t)src[at] << (8 * (i % 8));
+    }
+  }
+  return make_uint4((uint32_t)r[0], (uint32_t)(r[0] >> 32), (uint32_t)r[1], (uint32_t)(r[1] >> 32));
+}
+
+// k_batch_gather with the split folded in: the same contract (every 16-byte word of the staging buffer is
+// written, zeros outside the items, work cut by staged bytes, any source alignment, no read outside the
+// aligned 16-byte source words that overlap an item).  One thread per staged word.  A word that lies inside one
+// plane takes its 16 bytes from the 16 * E source bytes of 16 consecutive elements (E 16-byte loads, bytes
+// picked with v_perm_b32); the words that straddle planes go byte by byte; an item of width 1 is staged as
+// k_batch_gather stages it.
+__global__ __launch_bounds__(kGatherThreads) void k_batch_gather_planes(const BatchTyped* __restrict__ items, uint32_t n,
+                                                                        uint8_t* __restrict__ staged, uint64_t words)
+{
+  const uint64_t tiles = (words + kGatherTile - 1) / kGatherTile;
+  for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const uint64_t w0 = tile * kGatherTile;
+    const uint64_t w1 = w0 + kGatherTile < words ? w0 + kGatherTile : words;
+    const uint32_t first = item_at(items, 0, n, 16 * w0);
+    const uint32_t last = item_at(items, first, n, 16 * (w1 - 1));
+    for (uint64_t w = w0 + threadIdx.x; w < w1; w += kGatherThreads) {
+      const BatchTyped it = items[item_at(items, first, last + 1, 16 * w)];
+      uint64_t off = 16 * w - it.start;  // item-relative offset of the word
+      const uint32_t E = it.elem, lg = __ffs(E) - 1, m = it.size >> lg;
+      // Which word a thread takes is permuted inside the item: with wp = m / 16 whole words per plane, slot
+      // j * E + k takes word k * wp + j (a bijection of the first E * wp words, the rest keep their place).  E
+      // neighbouring lanes then build words of E different planes from the SAME 16 * E source bytes, so a
+      // wave's load touches 64 / E spans and not 64, and every source line is fetched once per wave and
+      // not by E waves far apart in the grid; the lanes of one plane still store 16 * 64 / E consecutive bytes.
+      if (E > 1) {
+        const uint64_t slot = off / 16, wp = m / 16;
+        if (slot < wp * E) off = 16 * ((slot & (E - 1)) * wp + (slot >> lg));
+      }
+      const uint64_t at = it.start + off;
+      uint4 v = make_uint4(0u, 0u, 0u, 0u);
+      if (off < it.size) {
+        const uint32_t o = (uint32_t)off;
+        if (E == 1) {
+          uint64_t r0, r1;
+          gather_word(it.src, it.size, o, r0, r1);
+          v = make_uint4((uint32_t)r0, (uint32_t)(r0 >> 32), (uint32_t)r1, (uint32_t)(r1 >> 32));
+        } else {
+          const uint8_t* src = reinterpret_cast<const uint8_t*>(it.src);
+          uint32_t k = 0, e = m;  // e + 16 <= m: the word lies inside plane k, from element e on
+          if (o + 16 <= m * E) {
+            k = o / m;
+            e = o - k * m;
+          }
+          if (e + 16 <= m) {
+            const uint8_t* p = src + (uint64_t)e * E;
+            v = E == 2 ? plane_word<2>(p, k) : E == 4 ? plane_word<4>(p, k) : plane_word<8>(p, k);
+          } else {
+            v = plane_bytes(src, it.size, E, m, o);
+          }
+        }
+      }
+      *reinterpret_cast<uint4*>(staged + at) = v;
+    }
+  }
+}
+
+// the bytes of output positions [lo, hi) (at most 16, in the aligned word that starts at `base`, which may lie
+// below 0) one by one, from item idx on: the items follow each other without gaps, none is empty
+__device__ __forceinline__ uint4 merge_bytes(const BatchTyped* __restrict__ items, uint32_t idx, const uint8_t* __restrict__ from,
+                                             int64_t base, uint64_t lo, uint64_t hi)
+{
+  BatchTyped it = items[idx];
+  uint64_t r0 = 0, r1 = 0;
+  for (uint64_t pos = lo; pos < hi; pos++) {
+    while (pos >= it.start + it.size) it = items[++idx];
+    const uint32_t b = (uint32_t)(pos - it.start), E = it.elem, lg = __ffs(E) - 1, m = it.size >> lg;
+    const uint32_t at = b < (m << lg) ? (b & (E - 1)) * m + (b >> lg) : b;
+    const uint32_t i = (uint32_t)((int64_t)pos - base);
+    const uint64_t x = (uint64_t)from[it.src + at] << (8 * (i % 8));
+    if (i < 8) r0 |= x;
+    else r1 |= x;
+  }
+  return make_uint4((uint32_t)r0, (uint32_t)(r0 >> 32), (uint32_t)r1, (uint32_t)(r1 >> 32));
+}
+
+// The inverse of the split, from the batch decoder's scratch (item i's split bytes at from + src) to the
+// caller's buffer (the item at to + start; `to` has any alignment, the items lie back to back).  One thread
+// per ALIGNED 16-byte word of the destination, work cut by bytes as in the gather.  A word inside one item
+// whose position in the item is a multiple of E (every word of an item that starts at a multiple of its
+// element width) takes 16 / E bytes from each plane -- unaligned loads inside the item's scratch extent --
+// and interleaves them with v_perm_b32; width 1 is one unaligned 16-byte load.  Every other word (another
+// phase, the tail, two items in one word) goes byte by byte, and the first and last words of the destination
+// store only the bytes inside [to, to + total).
+__global__ __launch_bounds__(kGatherThreads) void k_batch_merge(const BatchTyped* __restrict__ items, uint32_t n,
+                                                                const uint8_t* __restrict__ from, uint8_t* __restrict__ to,
+                                                                uint64_t total, uint64_t words)
+{
+  const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(to) & 15u);
+  const uint64_t tiles = (words + kGatherTile - 1) / kGatherTile;
+  for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const uint64_t w0 = tile * kGatherTile;
+    const uint64_t w1 = w0 + kGatherTile < words ? w0 + kGatherTile : words;
+    const uint32_t first = item_at(items, 0, n, w0 ? 16 * w0 - a0 : 0);
+    const uint32_t last = item_at(items, first, n, total - 1 < 16 * w1 - a0 - 1 ? total - 1 : 16 * w1 - a0 - 1);
+    for (uint64_t w = w0 + threadIdx.x; w < w1; w += kGatherThreads) {
+      const int64_t base = (int64_t)(16 * w) - a0;
+      const uint64_t lo = base < 0 ? 0 : (uint64_t)base;
+      const uint64_t hi = (uint64_t)(base + 16) < total ? (uint64_t)(base + 16) : total;
+      const uint32_t idx = item_at(items, first, last + 1, lo);
+      const BatchTyped it = items[idx];
+      const uint32_t b = (uint32_t)(lo - it.start), E = it.elem, lg = __ffs(E) - 1, m = it.size >> lg;
+      const uint8_t* p = from + it.src;
+      uint4 v;
+      if (hi - lo == 16 && b + 16 <= it.size && E == 1) {
+        const Unaligned16 x = *reinterpret_cast<const Unaligned16*>(p + b);
+        v = make_uint4(x.x, x.y, x.z, x.w);
+      } else if (hi - lo == 16 && b + 16 <= (m << lg) && !(b & (E - 1))) {
+        const uint8_t* q = p + (b >> lg);
+        if (E == 2) {
+          const Unaligned8 x = *reinterpret_cast<const Unaligned8*>(q), y = *reinterpret_cast<const Unaligned8*>(q + m);
+          v = make_uint4(perm(y.x, x.x, 0x05010400u), perm(y.x, x.x, 0x07030602u), perm(y.y, x.y, 0x05010400u),
+                         perm(y.y, x.y, 0x07030602u));
+        } else if (E == 4) {
+          uint32_t x[4];
+#pragma unroll
+          for (uint32_t k = 0; k < 4; k++) x[k] = reinterpret_cast<const Unaligned4*>(q + (uint64_t)k * m)->x;
+          const uint32_t l0 = perm(x[1], x[0], 0x05010400u), l1 = perm(x[3], x[2], 0x05010400u);
+          const uint32_t h0 = perm(x[1], x[0], 0x07030602u), h1 = perm(x[3], x[2], 0x07030602u);
+          v = make_uint4(perm(l1, l0, 0x05040100u), perm(l1, l0, 0x07060302u), perm(h1, h0, 0x05040100u),
+                         perm(h1, h0, 0x07060302u));
+        } else {
+          uint32_t t[4];
+#pragma unroll
+          for (uint32_t k = 0; k < 4; k++)
+            t[k] = perm(reinterpret_cast<const Unaligned2*>(q + (uint64_t)(2 * k + 1) * m)->x,
+                        reinterpret_cast<const Unaligned2*>(q + (uint64_t)(2 * k) * m)->x, 0x05010400u);
+          v = make_uint4(perm(t[1], t[0], 0x05040100u), perm(t[3], t[2], 0x05040100u), perm(t[1], t[0], 0x07060302u),
+                         perm(t[3], t[2], 0x07060302u));
+        }
+      } else {
+        v = merge_bytes(items, idx, from, base, lo, hi);
+      }
+      if (hi - lo == 16) {
+        *reinterpret_cast<uint4*>(to + lo) = v;
+      } else {
+        const uint64_t x0 = v.x | ((uint64_t)v.y << 32), x1 = v.z | ((uint64_t)v.w << 32);
+        for (uint64_t pos = lo; pos < hi; pos++) {
+          const uint32_t i = (uint32_t)((int64_t)pos - base);
+          to[pos] = (uint8_t)((i < 8 ? x0 : x1) >> (8 * (i % 8)));
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
 
 void launch_batch_gather(const BatchItem* items, uint32_t n, uint8_t* staged, uint64_t stagedBytes, hipStream_t s)
@@ -112,6 +341,24 @@ void launch_batch_gather(const BatchItem* items, uint32_t n, uint8_t* staged, ui
   const uint64_t tiles = (words + kGatherTile - 1) / kGatherTile;
   hipLaunchKernelGGL(k_batch_gather, dim3((uint32_t)(tiles < kGatherGrid ? tiles : kGatherGrid)), dim3(kGatherThreads), 0, s,
                      items, n, staged, words);
+}
+
+void launch_batch_gather_planes(const BatchTyped* items, uint32_t n, uint8_t* staged, uint64_t stagedBytes, hipStream_t s)
+{
+  const uint64_t words = stagedBytes / 16;
+  if (!n || !words) return;
+  const uint64_t tiles = (words + kGatherTile - 1) / kGatherTile;
+  hipLaunchKernelGGL(k_batch_gather_planes, dim3((uint32_t)(tiles < kGatherGrid ? tiles : kGatherGrid)), dim3(kGatherThreads), 0,
+                     s, items, n, staged, words);
+}
+
+void launch_batch_merge(const BatchTyped* items, uint32_t n, const uint8_t* from, uint8_t* to, uint64_t total, hipStream_t s)
+{
+  if (!n || !total) return;
+  const uint64_t words = ((reinterpret_cast<uintptr_t>(to) & 15u) + total + 15) / 16;
+  const uint64_t tiles = (words + kGatherTile - 1) / kGatherTile;
+  hipLaunchKernelGGL(k_batch_merge, dim3((uint32_t)(tiles < kGatherGrid ? tiles : kGatherGrid)), dim3(kGatherThreads), 0, s,
+                     items, n, from, to, total, words);
 }
 
 void launch_batch_move(const BatchMove* moves, uint32_t n, const uint8_t* from, uint8_t* to, hipStream_t s)

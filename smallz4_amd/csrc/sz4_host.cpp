@@ -238,8 +238,12 @@ struct sz4_ctx {
   // ragged batch API: the gather's item table, the block mover's table and the staging area of a piece that
   // runs as two pipeline runs (sz4_compress_batch_device); the batch decoder's extent table
   DevBuf batchItems, batchMoves, batchTmp, unBatch;
-  hipEvent_t evGather[2] = {};  // timing: around k_batch_gather
+  // typed batch decoder (sz4_unlz4_batch_typed_device): the decoded split items, and k_batch_merge's item table
+  DevBuf unPlanes, mergeItems;
+  hipEvent_t evGather[2] = {};  // timing: around k_batch_gather / k_batch_gather_planes
   float gatherMs = 0;
+  hipEvent_t evMerge[2] = {};   // timing: around k_batch_merge
+  float mergeMs = 0;
   bool unIndexSerial = getenv("SZ4_UNLZ4_INDEX") && atoi(getenv("SZ4_UNLZ4_INDEX")) == 0;  // A/B: the one-lane walk
   std::vector<UnBlock> hUn;
   std::vector<UnSub> hSub;
@@ -287,7 +291,8 @@ struct sz4_ctx {
             &dpSegs, &reach, &segState, &walkSegs, &walkState, &longFlag, &longBits, &segLong, &segTail, &dpRec, &work,
             &dictLast, &dictPrevH, &dictPrevX, &dictPH, &dictPE, &dictKeys, &dictTemp, &dictSc, &dictSnap, &dictRuns, &dictLz,
             &chunkOut[0], &chunkOut[1], &stagedS[0], &stagedS[1], &unBlk, &unMeta, &unFlags, &unFrame, &unDict,
-            &unOut, &unSeq, &unSubs, &unMasks, &unImage, &unIx, &batchItems, &batchMoves, &batchTmp, &unBatch};
+            &unOut, &unSeq, &unSubs, &unMasks, &unImage, &unIx, &batchItems, &batchMoves, &batchTmp, &unBatch,
+            &unPlanes, &mergeItems};
   }
 
   int fail(int code, const char* what, hipError_t e = hipSuccess)
@@ -1348,17 +1353,23 @@ bool batch_fits_lds(uint64_t size) { return (size + 8 + 3) / 4 * 4 <= find_lds_b
 
 // One pipeline run over the items idx[0..k) (caller indices, ascending, all non-empty): plan, gather,
 // compress into out[0, outCap).  bytes[k] receives each item's blockBytes word (size with the 4-byte word,
-// top bit = stored); the blocks lie back to back in idx order.
-int batch_run(sz4_ctx* c, const std::vector<uint64_t>& idx, const void* const* ptrs, const uint32_t* sizes, uint32_t maxChain,
-              uint8_t* out, uint64_t outCap, std::vector<uint32_t>& bytes, hipStream_t s)
+// top bit = stored); the blocks lie back to back in idx order.  elems (null: every item as it is) holds the
+// items' element widths: a run with an item wider than 1 is staged by k_batch_gather_planes, which splits
+// every item into its byte planes on the way (the plan is the same: a split item has its item's size).
+int batch_run(sz4_ctx* c, const std::vector<uint64_t>& idx, const void* const* ptrs, const uint32_t* sizes,
+              const uint8_t* elems, uint32_t maxChain, uint8_t* out, uint64_t outCap, std::vector<uint32_t>& bytes, hipStream_t s)
 {
   const uint32_t nb = (uint32_t)idx.size();
-  std::vector<BatchItem> items(nb);
+  bool planes = false;
+  for (uint32_t k = 0; elems && k < nb; k++) planes |= elems[idx[k]] > 1;
+  std::vector<BatchItem> items(planes ? 0 : nb);
+  std::vector<BatchTyped> typed(planes ? nb : 0);
   c->hBlocks.clear();
   uint64_t at = 0;
   for (uint32_t k = 0; k < nb; k++) {
     const uint64_t n = sizes[idx[k]];
-    items[k] = BatchItem{(uint64_t)(uintptr_t)ptrs[idx[k]], at, n};
+    if (planes) typed[k] = BatchTyped{(uint64_t)(uintptr_t)ptrs[idx[k]], at, (uint32_t)n, elems[idx[k]]};
+    else items[k] = BatchItem{(uint64_t)(uintptr_t)ptrs[idx[k]], at, n};
     Block B{};
     B.start = at;
     B.end = at + n;
@@ -1377,13 +1388,16 @@ int batch_run(sz4_ctx* c, const std::vector<uint64_t>& idx, const void* const* p
   const uint64_t stagedBytes = at + kPad;
   hipError_t e = hipSuccess;
   if (int r = reserve_all(c, stagedBytes)) return r;
+  static_assert(sizeof(BatchTyped) == sizeof(BatchItem), "one table size for both gathers");
   if ((e = c->staged.reserve(stagedBytes)) || (e = c->batchItems.reserve(nb * sizeof(BatchItem) + 64)))
     return c->fail(SZ4_E_NOMEM, "staging", e);
   // the item table goes up with the plan, on the call's stream; `items` lives until the run has finished
-  if ((e = hipMemcpyAsync(c->batchItems.p, items.data(), nb * sizeof(BatchItem), hipMemcpyHostToDevice, s)))
+  if ((e = hipMemcpyAsync(c->batchItems.p, planes ? (const void*)typed.data() : (const void*)items.data(), nb * sizeof(BatchItem),
+                          hipMemcpyHostToDevice, s)))
     return c->fail(SZ4_E_DEVICE, "upload items", e);
   if (c->timing) hipEventRecord(c->evGather[0], s);
-  launch_batch_gather(c->batchItems.as<BatchItem>(), nb, c->staged.as<uint8_t>(), stagedBytes, s);
+  if (planes) launch_batch_gather_planes(c->batchItems.as<BatchTyped>(), nb, c->staged.as<uint8_t>(), stagedBytes, s);
+  else launch_batch_gather(c->batchItems.as<BatchItem>(), nb, c->staged.as<uint8_t>(), stagedBytes, s);
   if (c->timing) hipEventRecord(c->evGather[1], s);
   uint64_t size = 0;
   if (int r = run_pipeline(c, maxChain, c->staged.as<uint8_t>(), nullptr, 0, false, out, outCap, &size, s)) return r;
@@ -1403,8 +1417,8 @@ int batch_run(sz4_ctx* c, const std::vector<uint64_t>& idx, const void* const* p
 // its place in d_out; a mixed piece compresses both runs into batchTmp and k_batch_move puts every block at
 // its caller-order offset -- no payload byte passes through the host.  ext[i] receives item i's bytes in
 // d_out (0 for an empty item); the piece occupies d_out[pos, pos + sum of ext).
-int batch_piece(sz4_ctx* c, uint64_t i0, uint64_t i1, const void* const* ptrs, const uint32_t* sizes, uint32_t maxChain,
-                uint8_t* dOut, uint64_t pos, uint32_t* ext, float* stageSum, hipStream_t s)
+int batch_piece(sz4_ctx* c, uint64_t i0, uint64_t i1, const void* const* ptrs, const uint32_t* sizes, const uint8_t* elems,
+                uint32_t maxChain, uint8_t* dOut, uint64_t pos, uint32_t* ext, float* stageSum, hipStream_t s)
 {
   std::vector<uint64_t> run[2];
   uint64_t bound[2] = {0, 0};
@@ -1422,7 +1436,7 @@ int batch_piece(sz4_ctx* c, uint64_t i0, uint64_t i1, const void* const* ptrs, c
   if (run[0].empty() || run[1].empty()) {
     const int k = run[0].empty() ? 1 : 0;
     if (run[k].empty()) return SZ4_OK;
-    if (int r = batch_run(c, run[k], ptrs, sizes, maxChain, dOut + pos, bound[k], bytes[k], s)) return r;
+    if (int r = batch_run(c, run[k], ptrs, sizes, elems, maxChain, dOut + pos, bound[k], bytes[k], s)) return r;
     add_stages();
     for (size_t j = 0; j < run[k].size(); j++) ext[run[k][j]] = bytes[k][j] & 0x7FFFFFFFu;
     return SZ4_OK;
@@ -1431,7 +1445,8 @@ int batch_piece(sz4_ctx* c, uint64_t i0, uint64_t i1, const void* const* ptrs, c
   if ((e = c->batchTmp.reserve(bound[0] + bound[1] + 64))) return c->fail(SZ4_E_NOMEM, "batch staging", e);
   const uint64_t base[2] = {0, bound[0]};
   for (int k = 0; k < 2; k++) {
-    if (int r = batch_run(c, run[k], ptrs, sizes, maxChain, c->batchTmp.as<uint8_t>() + base[k], bound[k], bytes[k], s))
+    if (int r = batch_run(c, run[k], ptrs, sizes, elems, maxChain, c->batchTmp.as<uint8_t>() + base[k], bound[k], bytes[k],
+                          s))
       return r;
     add_stages();
     for (size_t j = 0; j < run[k].size(); j++) ext[run[k][j]] = bytes[k][j] & 0x7FFFFFFFu;
@@ -1486,6 +1501,7 @@ int sz4_create(sz4_ctx** ctx, int device, uint64_t reserve_bytes)
   }
   for (auto& e : c->ev) hipEventCreate(&e);
   for (auto& e : c->evGather) hipEventCreate(&e);
+  for (auto& e : c->evMerge) hipEventCreate(&e);
   c->budget.bufs = c->all_buffers();
   for (DevBuf* b : c->budget.bufs) b->bud = &c->budget;
   c->budget.owner = c;
@@ -1513,6 +1529,8 @@ void sz4_destroy(sz4_ctx* c)
   for (auto& e : c->ev)
     if (e) hipEventDestroy(e);
   for (auto& e : c->evGather)
+    if (e) hipEventDestroy(e);
+  for (auto& e : c->evMerge)
     if (e) hipEventDestroy(e);
   delete c;
 }
@@ -1723,16 +1741,24 @@ uint64_t sz4_batch_bound(const uint32_t* sizes, uint64_t count)
   return b;
 }
 
-int sz4_compress_batch_device(sz4_ctx* c, const void* const* in_ptrs, const uint32_t* in_sizes, uint64_t count,
-                              uint32_t max_chain, void* d_out, uint64_t out_cap, uint64_t* out_offsets, void* stream)
+// sz4_compress_batch_device (elem_sizes null) and sz4_compress_batch_typed_device
+static int compress_batch(sz4_ctx* c, const void* const* in_ptrs, const uint32_t* in_sizes, const uint8_t* elem_sizes,
+                          uint64_t count, uint32_t max_chain, void* d_out, uint64_t out_cap, uint64_t* out_offsets, void* stream)
 {
   if (!c || !out_offsets || (count && (!in_ptrs || !in_sizes)) || max_chain > 65535)
     return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
   c->begin_call();
+  bool typed = false;
   for (uint64_t i = 0; i < count; i++) {
     if (in_sizes[i] > kBlockMax) return c->fail(SZ4_E_ARG, "item larger than 4 MiB");
     if (in_sizes[i] && !in_ptrs[i]) return c->fail(SZ4_E_ARG, "null item pointer");
+    if (elem_sizes) {
+      const uint8_t e = elem_sizes[i];
+      if (e != 1 && e != 2 && e != 4 && e != 8) return c->fail(SZ4_E_ARG, "element width is not 1, 2, 4 or 8");
+      typed |= e > 1;
+    }
   }
+  if (!typed) elem_sizes = nullptr;  // widths of 1 throughout: the plain call
   // the kernels write the blocks in place: refuse a buffer that could be overrun
   const uint64_t bound = sz4_batch_bound(in_sizes, count);
   if (out_cap < bound) return c->fail(SZ4_E_CAPACITY, "out_cap < sz4_batch_bound(sizes, count)");
@@ -1764,7 +1790,8 @@ int sz4_compress_batch_device(sz4_ctx* c, const void* const* in_ptrs, const uint
       staged += st;
       blocks++;
     }
-    const int r = batch_piece(c, i, j, in_ptrs, in_sizes, max_chain, (uint8_t*)d_out, pos, c->hostBytes.data(), stageSum, s);
+    const int r =
+        batch_piece(c, i, j, in_ptrs, in_sizes, elem_sizes, max_chain, (uint8_t*)d_out, pos, c->hostBytes.data(), stageSum, s);
     if (r == SZ4_E_NOMEM && blocks > 1 && piece > kPieceFloor) {
       piece = std::max<uint64_t>(kPieceFloor, piece / 2);
       continue;  // the same items again, in smaller pieces
@@ -1783,13 +1810,39 @@ int sz4_compress_batch_device(sz4_ctx* c, const void* const* in_ptrs, const uint
   }
 }
 
+int sz4_compress_batch_device(sz4_ctx* c, const void* const* in_ptrs, const uint32_t* in_sizes, uint64_t count,
+                              uint32_t max_chain, void* d_out, uint64_t out_cap, uint64_t* out_offsets, void* stream)
+{
+  return compress_batch(c, in_ptrs, in_sizes, nullptr, count, max_chain, d_out, out_cap, out_offsets, stream);
+}
+
+int sz4_compress_batch_typed_device(sz4_ctx* c, const void* const* in_ptrs, const uint32_t* in_sizes, const uint8_t* elem_sizes,
+                                    uint64_t count, uint32_t max_chain, void* d_out, uint64_t out_cap, uint64_t* out_offsets,
+                                    void* stream)
+{
+  if (count && !elem_sizes) return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
+  return compress_batch(c, in_ptrs, in_sizes, elem_sizes, count, max_chain, d_out, out_cap, out_offsets, stream);
+}
+
 float sz4_last_gather_ms(sz4_ctx* c) { return c ? c->gatherMs : 0.0f; }
 
-int sz4_unlz4_batch_device(sz4_ctx* c, const void* d_blocks, const uint64_t* offsets, uint64_t count, void* d_out,
-                           uint64_t out_cap, uint64_t* out_offsets, void* stream)
+float sz4_last_merge_ms(sz4_ctx* c) { return c ? c->mergeMs : 0.0f; }
+
+// sz4_unlz4_batch_device (elem_sizes null: the blocks decode straight into d_out) and
+// sz4_unlz4_batch_typed_device (they decode into unPlanes, and k_batch_merge writes d_out)
+static int unlz4_batch(sz4_ctx* c, const void* d_blocks, const uint64_t* offsets, const uint8_t* elem_sizes, uint64_t count,
+                       void* d_out, uint64_t out_cap, uint64_t* out_offsets, void* stream)
 {
   if (!c || !out_offsets || (count && !offsets)) return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
   c->begin_call();
+  c->mergeMs = 0;
+  bool typed = false;
+  for (uint64_t i = 0; elem_sizes && i < count; i++) {
+    const uint8_t e = elem_sizes[i];
+    if (e != 1 && e != 2 && e != 4 && e != 8) return c->fail(SZ4_E_ARG, "element width is not 1, 2, 4 or 8");
+    typed |= e > 1;
+  }
+  if (!typed) elem_sizes = nullptr;  // widths of 1 throughout: the plain call
   DeviceGuard guard(c->device);
   try {
   hipStream_t s = (hipStream_t)stream;
@@ -1846,18 +1899,49 @@ int sz4_unlz4_batch_device(sz4_ctx* c, const void* d_blocks, const uint64_t* off
   for (; i <= count; i++) out_offsets[i] = w;
   if (w > out_cap || (w && !d_out)) return c->fail(SZ4_E_CAPACITY, "output buffer too small");
   if (!w) return SZ4_OK;
+  // typed: the blocks decode to the same offsets of a context buffer, and every item is merged on its way out
+  uint8_t* target = (uint8_t*)d_out;
+  std::vector<BatchTyped> merge;
+  if (elem_sizes) {
+    for (uint32_t b = 0; b < nb; b++)
+      if (c->hUn[b].size) merge.push_back(BatchTyped{c->hUn[b].dst, c->hUn[b].dst, (uint32_t)c->hUn[b].size, elem_sizes[item[b]]});
+    if ((e = c->unPlanes.reserve(w + 64)) || (e = c->mergeItems.reserve(merge.size() * sizeof(BatchTyped) + 64)))
+      return c->fail(SZ4_E_NOMEM, "typed decoder scratch", e);
+    target = c->unPlanes.as<uint8_t>();
+    if ((e = hipMemcpyAsync(c->mergeItems.p, merge.data(), merge.size() * sizeof(BatchTyped), hipMemcpyHostToDevice, s)))
+      return c->fail(SZ4_E_DEVICE, "upload items", e);
+  }
   if ((e = hipMemcpyAsync(c->unBlk.p, c->hUn.data(), nb * sizeof(UnBlock), hipMemcpyHostToDevice, s)) ||
       (e = hipMemsetAsync(status, 0, 4, s)))
     return c->fail(SZ4_E_DEVICE, "decoder plan", e);
-  launch_unlz4_blocks_indep(f, n, c->unBlk.as<UnBlock>(), nb, c->unSeq.as<uint4>(), (uint8_t*)d_out, status, s);
+  launch_unlz4_blocks_indep(f, n, c->unBlk.as<UnBlock>(), nb, c->unSeq.as<uint4>(), target, status, s);
+  if (elem_sizes) {
+    if (c->timing) hipEventRecord(c->evMerge[0], s);
+    launch_batch_merge(c->mergeItems.as<BatchTyped>(), (uint32_t)merge.size(), target, (uint8_t*)d_out, w, s);
+    if (c->timing) hipEventRecord(c->evMerge[1], s);
+  }
   if ((e = hipGetLastError()) || (e = hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, s)) ||
       (e = hipStreamSynchronize(s)))
     return c->fail(SZ4_E_DEVICE, "decode", e);
   if (st) return c->fail(SZ4_E_DEVICE, "decoded length differs from the size pass");
+  if (elem_sizes && c->timing && hipEventElapsedTime(&c->mergeMs, c->evMerge[0], c->evMerge[1]) != hipSuccess) c->mergeMs = 0;
   return SZ4_OK;
   } catch (const std::bad_alloc&) {
     return c->fail(SZ4_E_NOMEM, "host allocation");
   }
+}
+
+int sz4_unlz4_batch_device(sz4_ctx* c, const void* d_blocks, const uint64_t* offsets, uint64_t count, void* d_out,
+                           uint64_t out_cap, uint64_t* out_offsets, void* stream)
+{
+  return unlz4_batch(c, d_blocks, offsets, nullptr, count, d_out, out_cap, out_offsets, stream);
+}
+
+int sz4_unlz4_batch_typed_device(sz4_ctx* c, const void* d_blocks, const uint64_t* offsets, const uint8_t* elem_sizes,
+                                 uint64_t count, void* d_out, uint64_t out_cap, uint64_t* out_offsets, void* stream)
+{
+  if (count && !elem_sizes) return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
+  return unlz4_batch(c, d_blocks, offsets, elem_sizes, count, d_out, out_cap, out_offsets, stream);
 }
 
 int sz4_lz4_stream(sz4_ctx* c, sz4_get_bytes get_bytes, sz4_send_bytes send_bytes, uint32_t max_chain, const void* dict,

@@ -260,6 +260,19 @@ struct BatchItem {
 // stages the items and zero-fills every other byte of staged[0, stagedBytes) (the gaps between items and the
 // pad after the last one); stagedBytes is a multiple of 16 and `staged` 16-byte aligned
 void launch_batch_gather(const BatchItem* items, uint32_t n, uint8_t* staged, uint64_t stagedBytes, hipStream_t s);
+// typed items (sz4_compress_batch_typed_device / sz4_unlz4_batch_typed_device): an item of element width
+// `elem` (1, 2, 4 or 8).  For the gather src is a device address and start the staged offset, as in BatchItem;
+// for the merge src is the item's offset in the decoder's scratch and start its offset in the caller's buffer
+struct BatchTyped {
+  uint64_t src, start;
+  uint32_t size, elem;
+};
+// launch_batch_gather with the byte-plane split of every item of width > 1 folded in (the staged item is
+// split(item, elem): byte k of every whole element together, plane after plane, then the tail bytes)
+void launch_batch_gather_planes(const BatchTyped* items, uint32_t n, uint8_t* staged, uint64_t stagedBytes, hipStream_t s);
+// the inverse: to[start, start + size) = merge(from[src, src + size), elem) for every item; the items are
+// non-empty, ascending and back to back in `to` (starts are running sums from 0 to `total`); `to` has any alignment
+void launch_batch_merge(const BatchTyped* items, uint32_t n, const uint8_t* from, uint8_t* to, uint64_t total, hipStream_t s);
 // moves compressed blocks to their caller-order place: entry k copies len bytes from `from + src` to `to + dst`
 // (the host cuts long blocks into entries of at most kBatchMoveMax bytes, so the work is balanced by bytes)
 constexpr uint64_t kBatchMoveMax = 65536;

@@ -8,7 +8,8 @@ runs one warm-up and --reps timed calls in a row (so (a) keeps its cached plan, 
 whole sequence runs --rounds times so that drift shows; rates are means over all timed calls with the
 min..max spread, the stage split and the gather time are the last call's.  The batch legs' times include
 the Python binding's marshalling of the pointer and size lists.
-    python3 tools/time_batch.py [--mb 100] [--reps 5] [--rounds 2] [--chain 65535]"""
+    python3 tools/time_batch.py [--mb 100] [--reps 5] [--rounds 2] [--chain 65535]
+With --elem 2,4,8 it times the typed batch API's two kernels instead (see typed() below)."""
 import argparse
 import os
 import random
@@ -23,13 +24,82 @@ import smallz4_amd  # noqa: E402
 from smallz4_amd import synth  # noqa: E402
 
 
+def median(xs):
+    xs = sorted(xs)
+    return xs[len(xs) // 2] if len(xs) % 2 else (xs[len(xs) // 2 - 1] + xs[len(xs) // 2]) / 2
+
+
+def typed(a):
+    """--elem: the split gather (k_batch_gather_planes) against the plain gather on the same items, and the
+    merge (k_batch_merge) against a device-to-device copy of the same bytes.  Item sets: 1526 items of
+    64 KiB, 10 000 items of 200 bytes to 4 KiB, and those cut down to whole elements; medians of the device
+    times over reps x rounds calls."""
+    import numpy as np
+    dev = torch.device("cuda:0")
+    widths = [1] + [int(x) for x in a.elem.split(",") if int(x) != 1]
+    rng = random.Random(9)
+    small = [rng.randrange(200, 4097) for _ in range(10000)]
+    # the third set is the second with whole elements only: every item then lands at a multiple of its width
+    sets = {"1526 x 64 KiB": [65536] * 1526, "10000 x 200 B..4 KiB": small,
+            "10000 x 200 B..4 KiB, multiples of 8": [k & ~7 for k in small]}
+    comp = smallz4_amd.Compressor()
+    comp.set_timing(True)
+    for label, sizes in sets.items():
+        n = sum(sizes)
+        g = np.random.default_rng(9)
+        data = (np.cumsum(g.integers(0, 70000, n // 4 + 1)) & 0x7FFFFFFF).astype(np.int32).tobytes()[:n]
+        t_in = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+        ptrs, at = [], 0
+        for k in sizes:
+            ptrs.append(t_in.data_ptr() + at)
+            at += k
+        cap = comp.batch_bound(sizes) + 64
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        dec = torch.empty(n, dtype=torch.uint8, device=dev)
+        dup = torch.empty(n, dtype=torch.uint8, device=dev)
+        copies = []
+        for _ in range(a.reps * a.rounds + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            dup.copy_(t_in)
+            e1.record()
+            torch.cuda.synchronize()
+            copies.append(e0.elapsed_time(e1))
+        copy_ms = median(copies[1:])
+        print(f"{label}: {n} bytes, device-to-device copy {copy_ms:.4f} ms [{min(copies[1:]):.4f} .. {max(copies[1:]):.4f}]",
+              flush=True)
+        base = None
+        for E in widths:
+            elems = [E] * len(sizes)
+            gather, merge = [], []
+            for rep in range(a.reps * a.rounds + 1):
+                off = comp.compress_batch_typed_device(ptrs, sizes, elems, out.data_ptr(), cap, a.chain)
+                g_ms = comp.last_gather_ms()
+                got = comp.unlz4_batch_typed_device(out.data_ptr(), off, elems, dec.data_ptr(), n)
+                m_ms = comp.last_merge_ms()
+                assert got[-1] == n and torch.equal(dec, t_in), (label, E)
+                if rep:
+                    gather.append(g_ms)
+                    merge.append(m_ms)
+            g_ms, m_ms = median(gather), median(merge)
+            base = g_ms if E == 1 else base
+            line = (f"  E={E}: gather {g_ms:.4f} ms [{min(gather):.4f} .. {max(gather):.4f}] ({g_ms / base:.2f}x the plain "
+                    f"gather), {off[-1]} bytes out")
+            if E > 1:
+                line += f", merge {m_ms:.4f} ms [{min(merge):.4f} .. {max(merge):.4f}] ({m_ms / copy_ms:.2f}x the copy)"
+            print(line, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mb", type=float, default=100)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--chain", type=int, default=65535)
     ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--elem", default="", help="element widths, e.g. 2,4,8: time the typed gather and merge instead")
     a = ap.parse_args()
+    if a.elem:
+        return typed(a)
     n = int(a.mb * 1e6)
     data = synth.enwik8_like(n, seed=8)
     dev = torch.device("cuda:0")
