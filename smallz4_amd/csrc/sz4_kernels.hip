@@ -1143,10 +1143,12 @@ __device__ __forceinline__ void find_sorted_body(const uint8_t* __restrict__ in,
       // keys and queue entries carry the candidate's window-relative POSITION (17 bits): inside one key
       // group positions ascend with the slots, so the maximum is the same, and no slot array is read to
       // turn a key into a distance (a global load in the flush would make the compiler wait on the
-      // below-chunk prefetch at every step after it).  Shift-register step sh: the candidate is lane
-      // (lane - sh)'s own position; broadcast candidate k: lane k's fRel
-      auto spos = [&](uint32_t sh) -> uint32_t {
-        return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((lane - sh) & 63u) << 2), (int)myRel);
+      // below-chunk prefetch at every step after it).  Broadcast candidate k: lane k's fRel.  While the
+      // shift register runs, a key carries the candidate's source LANE instead (step sh: lane - sh):
+      // positions ascend with the lanes of one key group, so the order is the same, and relOf() turns
+      // bestKey into the position form once per chunk (and a queue entry when it is queued), not per hit
+      auto relOf = [&](uint32_t srcLane) -> uint32_t {
+        return (uint32_t)__builtin_amdgcn_ds_bpermute((int)((srcLane & 63u) << 2), (int)myRel);
       };
       auto flush = [&]() {
         // lane t extends queue entry base + t: target = lane (e >> 17), candidate position e & 0x1FFFF
@@ -1251,6 +1253,7 @@ __device__ __forceinline__ void find_sorted_body(const uint8_t* __restrict__ in,
       auto setMasks = [&]() {
         const uint32_t len = bestKey >> 17;
         const uint32_t bits = len >= cap12 ? 63u : min(8u * len - 24u, 63u);
+        // (the 64-bit shift and subtract measured faster than a 32-bit bit-field mask and two selects)
         const uint64_t mk = (1ull << bits) - 1ull;
         m1 = (uint32_t)mk;
         m2 = (uint32_t)(mk >> 32);
@@ -1258,29 +1261,32 @@ __device__ __forceinline__ void find_sorted_body(const uint8_t* __restrict__ in,
       auto filt = [&](uint32_t k0, uint32_t k1, uint32_t k2) -> uint32_t {
         return (k0 ^ me0) | ((k1 ^ me1) & m1) | ((k2 ^ me2) & m2);
       };
-      // the hit, from the candidate's words already xor-ed with the lane's own (x0 = 0: same first word)
-      auto hitx = [&](bool mine, uint32_t cs, uint32_t x0, uint32_t x1, uint32_t x2) {
+      // the hit, from the candidate's words already xor-ed with the lane's own.  pass: the step's own
+      // predicate (a live lane of the same first word whose candidate passed the mask) -- every other
+      // candidate of the lane's key is no longer than the lane's best and farther, so its key could not
+      // raise the maximum.  laneForm: cs is the candidate's source lane (shift register), else its position
+      auto hitx = [&](auto laneForm, bool pass, uint32_t cs, uint32_t x1, uint32_t x2) {
         SZ4_D3(dBi++;)  // hit branches (wave-level)
         // v_ffbl_b32 gives ~0u for 0, so min() takes x2 when x1 is 0 (no compare and select)
         const uint32_t z = min(ffbl(x1), 32u + min(ffbl(x2), 32u));
         const uint32_t lcp = min(4u + (z >> 3), cap12);
-        const uint32_t key = (mine && x0 == 0u) ? (lcp << 17) | cs : 0u;
+        const uint32_t key = pass ? (lcp << 17) | cs : 0u;
         bestKey = key > bestKey ? key : bestKey;
         setMasks();
-        // queued: 12 bytes equal, and the match may grow past them (the lane's own bit of the ballot, not
-        // the predicate again: one compare instead of a materialised bool compared twice)
-        const uint64_t sat = __ballot(mine && (x0 | x1 | x2 | noGrow) == 0u);
+        // queued: 12 bytes equal (they pass every mask), and the match may grow past them
+        const uint64_t sat = __ballot(pass && (x1 | x2 | noGrow) == 0u);
         if (sat) {
           const uint32_t at = qn + (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(sat >> 32),
                                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)sat, 0u));
-          if ((sat >> lane) & 1ull) satQ[at] = (lane << 17) | cs;
+          // the queue holds positions only (flush, satBest)
+          const uint32_t crel = decltype(laneForm)::value ? relOf(cs) : cs;
+          if ((sat >> lane) & 1ull) satQ[at] = (lane << 17) | crel;
           qn += (uint32_t)__builtin_popcountll(sat);
           if (qn >= 64) flush();
         }
       };
-      auto hit = [&](bool mine, uint32_t cs, uint32_t k0, uint32_t k1, uint32_t k2) {
-        hitx(mine, cs, k0 ^ me0, k1 ^ me1, k2 ^ me2);
-      };
+      constexpr std::true_type kLaneForm{};
+      constexpr std::false_type kPosForm{};
       setMasks();
       // 1. inside the chunk: shift register (after s shifts lane l holds slot first + l - s)
       {
@@ -1321,7 +1327,8 @@ __device__ __forceinline__ void find_sorted_body(const uint8_t* __restrict__ in,
             r1 = shr1(r1);
             r2 = shr1(r2);
             const uint32_t y = ((r0 ^ me0) | dead) | ((r1 ^ me1) & m1) | ((r2 ^ me2) & m2);
-            if (__ballot(y == 0u)) hit(s <= myCnt, spos(s), r0, r1, r2);
+            // (the zeros shifted in below lane 0 equal a key of four zero bytes: the lane's bound stays)
+            if (__ballot(y == 0u)) hitx(kLaneForm, y == 0u && s <= myCnt, lane - s, r1 ^ me1, r2 ^ me2);
           }
         } else {
           for (; s <= trips; s++) {
@@ -1331,15 +1338,13 @@ __device__ __forceinline__ void find_sorted_body(const uint8_t* __restrict__ in,
             r2 = shr1(r2);
             const uint32_t dead = s <= myCnt ? 0u : ~0u;
             const uint32_t y = ((r0 ^ me0) | dead) | ((r1 ^ me1) & m1) | ((r2 ^ me2) & m2);
-            if (__ballot(y == 0u)) hit(s <= myCnt, spos(s), r0, r1, r2);
+            if (__ballot(y == 0u)) hitx(kLaneForm, y == 0u, lane - s, r1 ^ me1, r2 ^ me2);
           }
         }
-        for (; s <= trips; s++) {
-          SZ4_D3(dL++;)
-          r0 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r0, kWaveShr1, 0xF, 0xF, false);
-          r1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r1, kWaveShr1, 0xF, 0xF, false);
-          r2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r2, kWaveShr1, 0xF, 0xF, false);
-          visit(s <= myCnt, spos(s), r0, r1, r2);
+        // bestKey into the position form: one lane read per chunk (length 3: no match, nothing to turn)
+        {
+          const uint32_t brel = relOf(bestKey);
+          if (bestKey >= (4u << 17)) bestKey = (bestKey & ~0x1FFFFu) | brel;
         }
         run = run && (int32_t)gs < (int32_t)first;
       }
@@ -1390,8 +1395,8 @@ __device__ __forceinline__ void find_sorted_body(const uint8_t* __restrict__ in,
                 const uint32_t x0 = (uint32_t)__builtin_amdgcn_mov_dpp((int)g0, 0x150 + (K), 0xF, 0xF, true) ^ me0; \
                 const uint32_t x1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)g1, 0x150 + (K), 0xF, 0xF, true) ^ me1; \
                 const uint32_t x2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)g2, 0x150 + (K), 0xF, 0xF, true) ^ me2; \
-                if (__ballot((K) < kcRel && (x0 | (x1 & m1) | (x2 & m2)) == 0u))                                 \
-                  hitx((K) < kcRel, rdlane(fRel, (uint32_t)(q0 + (K))), x0, x1, x2);                                    \
+                const bool h = (K) < kcRel && (x0 | (x1 & m1) | (x2 & m2)) == 0u;                                 \
+                if (__ballot(h)) hitx(kPosForm, h, rdlane(fRel, (uint32_t)(q0 + (K))), x1, x2);                   \
               }
               SZ4_BSTEP_W(0) SZ4_BSTEP_W(1) SZ4_BSTEP_W(2) SZ4_BSTEP_W(3) SZ4_BSTEP_W(4) SZ4_BSTEP_W(5)
               SZ4_BSTEP_W(6) SZ4_BSTEP_W(7) SZ4_BSTEP_W(8) SZ4_BSTEP_W(9) SZ4_BSTEP_W(10) SZ4_BSTEP_W(11)
@@ -1434,7 +1439,8 @@ __device__ __forceinline__ void find_sorted_body(const uint8_t* __restrict__ in,
                   if ((todo >> (K)) & 1u) {                                                                     \
                     const uint32_t x1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)g1, 0x150 + (K), 0xF, 0xF, true) ^ me1; \
                     const uint32_t x2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)g2, 0x150 + (K), 0xF, 0xF, true) ^ me2; \
-                    if (__ballot(((x1 & m1) | (x2 & m2)) == 0u)) hitx(true, rdlane(fRel, (uint32_t)(q0 + (K))), 0u, x1, x2); \
+                    const bool h = ((x1 & m1) | (x2 & m2)) == 0u;                                               \
+                    if (__ballot(h)) hitx(kPosForm, h, rdlane(fRel, (uint32_t)(q0 + (K))), x1, x2);             \
                   }
                   SZ4_BSTEP_S(0) SZ4_BSTEP_S(1) SZ4_BSTEP_S(2) SZ4_BSTEP_S(3) SZ4_BSTEP_S(4) SZ4_BSTEP_S(5)
                   SZ4_BSTEP_S(6) SZ4_BSTEP_S(7) SZ4_BSTEP_S(8) SZ4_BSTEP_S(9) SZ4_BSTEP_S(10) SZ4_BSTEP_S(11)
@@ -1447,7 +1453,8 @@ __device__ __forceinline__ void find_sorted_body(const uint8_t* __restrict__ in,
                     const uint32_t x0 = (uint32_t)__builtin_amdgcn_mov_dpp((int)g0, 0x150 + (K), 0xF, 0xF, true) ^ me0; \
                     const uint32_t x1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)g1, 0x150 + (K), 0xF, 0xF, true) ^ me1; \
                     const uint32_t x2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)g2, 0x150 + (K), 0xF, 0xF, true) ^ me2; \
-                    if (__ballot((x0 | (x1 & m1) | (x2 & m2)) == 0u)) hitx(true, rdlane(fRel, (uint32_t)(q0 + (K))), x0, x1, x2); \
+                    const bool h = (x0 | (x1 & m1) | (x2 & m2)) == 0u;                                          \
+                    if (__ballot(h)) hitx(kPosForm, h, rdlane(fRel, (uint32_t)(q0 + (K))), x1, x2);             \
                   }
                   SZ4_BSTEP_N(0) SZ4_BSTEP_N(1) SZ4_BSTEP_N(2) SZ4_BSTEP_N(3) SZ4_BSTEP_N(4) SZ4_BSTEP_N(5)
                   SZ4_BSTEP_N(6) SZ4_BSTEP_N(7) SZ4_BSTEP_N(8) SZ4_BSTEP_N(9) SZ4_BSTEP_N(10) SZ4_BSTEP_N(11)
@@ -1466,14 +1473,16 @@ __device__ __forceinline__ void find_sorted_body(const uint8_t* __restrict__ in,
                 todo &= todo - 1ull;
                 SZ4_D3(dB++;)
                 const uint32_t k1 = rdlane(f1, kk), k2 = rdlane(f2, kk);
-                if (__ballot((((k1 ^ me1) & m1) | ((k2 ^ me2) & m2)) == 0u)) hit(true, rdlane(fRel, kk), me0u, k1, k2);
+                const bool h = (((k1 ^ me1) & m1) | ((k2 ^ me2) & m2)) == 0u;
+                if (__ballot(h)) hitx(kPosForm, h, rdlane(fRel, kk), k1 ^ me1, k2 ^ me2);
               }
               k = n;
             }
             for (; k < n; k++) {
               SZ4_D3(dB++;)
               const uint32_t k0 = rdlane(f0, k), k1 = rdlane(f1, k), k2 = rdlane(f2, k);
-              if (__ballot(filt(k0, k1, k2) == 0u)) hit(true, rdlane(fRel, (uint32_t)k), k0, k1, k2);
+              const bool h = filt(k0, k1, k2) == 0u;
+              if (__ballot(h)) hitx(kPosForm, h, rdlane(fRel, (uint32_t)k), k1 ^ me1, k2 ^ me2);
             }
             for (; k + 1 < n; k += 2) {
               SZ4_D3(dB += 2;)
@@ -2142,6 +2151,14 @@ __device__ __forceinline__ void find_long9_body(const uint8_t* __restrict__ in, 
   int32_t* skip = reinterpret_cast<int32_t*>(skipAll + S.elemOff);
   const Interval* iv = ivAll + (uint64_t)S.block * kMaxIv;
   const uint32_t niv = ivCount[S.block];
+  if (!fixMode && segLong[blockIdx.x] == 0u) {
+    // pass 1 left no long or big target here, so only the block's own shortcut-interval targets (marked,
+    // never sorted) could need this pass: without one in [s0, s1) leave before the window is staged
+    // (uniform: every thread reads the same words)
+    bool own = false;
+    for (uint32_t k = 0; k < niv; k++) own |= iv[k].lo < S.s1 && iv[k].hi > S.s0;
+    if (!own) return;
+  }
   if (fixMode) {
     // the repair pass has work only where a piece head's speculative carry differs from its
     // predecessor's final result (the same test as below): otherwise leave before staging the window
