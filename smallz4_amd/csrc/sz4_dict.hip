@@ -973,16 +973,16 @@ uint64_t dict_sort_temp_bytes()
 
 int launch_dict_parallel(const DictArgs& A, hipStream_t s)
 {
-  const uint32_t nb = A.nb;
+  const uint32_t nb = A.nblocks;
   if (!nb) return 0;
   const uint64_t runLo = A.hBlocks[0].start, runHi = A.hBlocks[nb - 1].end;
   const uint64_t runBase = runLo & ~63ull, runChunks = (runHi - runBase) / 64;
-  DictPlan P{A.dBlocks, nb, A.cont, A.dictBack, A.low0, A.legacy ? 1u : 0u, A.iv, A.ivCount, A.runTab, runBase, runChunks};
+  DictPlan P{A.blocks, nb, A.cont, A.dictBack, A.low0, A.legacy ? 1u : 0u, A.iv, A.ivCount, A.runTab, runBase, runChunks};
   if (A.buildRuns && runChunks) {
     hipLaunchKernelGGL(k_dict_run_flags, dim3((uint32_t)((runChunks + 255) / 256)), dim3(256), 0, s, A.in, runBase, runChunks,
                        A.runFlag);
     hipLaunchKernelGGL(k_dict_runs, dim3((uint32_t)((runChunks + 63) / 64)), dim3(64), 0, s, A.in, runBase, runChunks, runLo,
-                       runHi, A.runFlag, A.runTab, A.dBlocks, nb, A.legacy ? 1u : 0u, A.guess ? A.iv : nullptr, A.ivCount);
+                       runHi, A.runFlag, A.runTab, A.blocks, nb, A.legacy ? 1u : 0u, A.guess ? A.iv : nullptr, A.ivCount);
     if (A.guess) hipLaunchKernelGGL(k_dict_guess_sort, dim3((nb + 63) / 64), dim3(64), 0, s, nb, A.iv, A.ivCount);
   }
   if (!A.legacy)
@@ -1012,12 +1012,12 @@ int launch_dict_parallel(const DictArgs& A, hipStream_t s)
   hipLaunchKernelGGL(k_dict_search, dim3((maxSize + 4 * kDictSearchSpan - 1) / (4 * kDictSearchSpan), nb), dim3(256), 0, s, A.in, P, A.maxChain, A.pe, A.prevX,
                      A.mlen, A.mdist, A.sel, A.longFlag);
   if (A.maxChain <= (uint32_t)kLazyMax && A.nwalk) {
-    hipLaunchKernelGGL(k_dict_lz_walk, dim3((A.nwalk + 3) / 4), dim3(256), 0, s, A.dBlocks, A.walkSegs, A.nwalk, A.mlen,
-                       A.pe, A.lzMasks, A.lzState);
-    hipLaunchKernelGGL(k_dict_lz_join, dim3((A.nwalk + 3) / 4), dim3(256), 0, s, A.dBlocks, A.walkSegs, A.nwalk, A.mlen,
-                       A.pe, A.lzMasks, A.lzState);
-    hipLaunchKernelGGL(k_dict_lz_fix, dim3(nb), dim3(64), 0, s, A.dBlocks, A.mlen, A.pe, A.lzMasks, A.lzState);
-    hipLaunchKernelGGL(k_dict_lz_clear, dim3((A.nwalk + 3) / 4), dim3(256), 0, s, A.dBlocks, A.walkSegs, A.nwalk, A.mlen,
+    hipLaunchKernelGGL(k_dict_lz_walk, dim3((A.nwalk + 3) / 4), dim3(256), 0, s, A.blocks, A.walkSegs, A.nwalk, A.mlen,
+                       A.pe, A.lzMasks, A.walkState);
+    hipLaunchKernelGGL(k_dict_lz_join, dim3((A.nwalk + 3) / 4), dim3(256), 0, s, A.blocks, A.walkSegs, A.nwalk, A.mlen,
+                       A.pe, A.lzMasks, A.walkState);
+    hipLaunchKernelGGL(k_dict_lz_fix, dim3(nb), dim3(64), 0, s, A.blocks, A.mlen, A.pe, A.lzMasks, A.walkState);
+    hipLaunchKernelGGL(k_dict_lz_clear, dim3((A.nwalk + 3) / 4), dim3(256), 0, s, A.blocks, A.walkSegs, A.nwalk, A.mlen,
                        A.mdist, A.pe, A.lzMasks, A.longFlag);
   }
   if (!A.legacy) hipLaunchKernelGGL(k_dict_carry, dim3(65536 / 256), dim3(256), 0, s, P, A.ph, A.pe, A.prevH, A.prevX);
@@ -1025,7 +1025,7 @@ int launch_dict_parallel(const DictArgs& A, hipStream_t s)
   const uint64_t wpb = (maxSize + 63) / 64;
   hipLaunchKernelGGL(k_dict_sc_bits, dim3((uint32_t)((wpb * 64 + 255) / 256), nb), dim3(256), 0, s, P, A.mlen, A.mdist,
                      A.scBits, wpb);
-  hipLaunchKernelGGL(k_dict_sc, dim3(nb), dim3(64), 0, s, A.dBlocks, A.scBits, wpb, A.mlen, A.iv, A.ivCount, A.status);
+  hipLaunchKernelGGL(k_dict_sc, dim3(nb), dim3(64), 0, s, A.blocks, A.scBits, wpb, A.mlen, A.iv, A.ivCount, A.status);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

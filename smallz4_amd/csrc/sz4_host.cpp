@@ -227,11 +227,9 @@ struct sz4_ctx {
   bool batchChunked = false;           // the last sz4_compress_blocks_device call ran in several pieces
   uint64_t streamPlanKey[5] = {~0ull, 0, 0, 0, 0};  // stream path: the chunk shape the current plan is for
   // stream path, chunk continuation: the previous chunk's last block's final shortcut intervals
-  // (ghost slot nblocks of iv/ivCount, B.prev of the first block) and dictionary-mode state
+  // (ghost slot nblocks of iv/ivCount, B.prev of the first block), uploaded by runs whose RunMode says so
   std::vector<Interval> ghostIv;
   uint32_t ghostN = 0;
-  bool ghost = false;
-  uint32_t dictCont = 0, dictShift = 0, dictLow0 = 0;
   DevBuf unBlk, unMeta, unFlags, unFrame, unDict, unOut, unSeq;  // decoder (sz4_unlz4*)
   DevBuf unSubs, unMasks, unImage;  // decoder split mode: sub-segments, their token-start masks, the u32 image
   DevBuf unIx;                       // decoder: the parallel frame index's candidates and successors
@@ -251,8 +249,6 @@ struct sz4_ctx {
   uint32_t unResolvePasses = 0;  // the longest reference chain the last split-mode decode's pack followed
   bool unIndexParallel = false;  // the last frame index came from the parallel index (not the serial walk)
   int unSplitMode = getenv("SZ4_UNLZ4_SPLIT") ? atoi(getenv("SZ4_UNLZ4_SPLIT")) : -1;  // -1 auto, 0 never, 1 always
-  int64_t dictBack = -1;       // >= 0: dictionary mode, first insertion this far before the first block
-  int dictLegacy = 0;
   bool dictSerial = getenv("SZ4_DICT_SERIAL") != nullptr;  // A/B and tests: the in-order replay for every chunk
 
   std::vector<Block> hBlocks;
@@ -306,6 +302,19 @@ struct sz4_ctx {
 };
 
 namespace {
+
+// an independent block over the staged bytes [start, end): it sees nothing before its first byte
+Block independent_block(uint64_t start, uint64_t end, uint32_t flags = 0)
+{
+  Block B{};
+  B.start = start;
+  B.end = end;
+  B.low = start;
+  B.cut = kNone;
+  B.prev = kNoBlock;
+  B.flags = flags;
+  return B;
+}
 
 // Targets of block B are positions [start, end - 11) (smallz4.h:629); the window of a segment
 // reaches back 64 KiB - 1 but never below the block's lowest visible byte.
@@ -441,10 +450,71 @@ void mark(sz4_ctx* c, int i, hipStream_t s)
 int pipeline_finish(sz4_ctx* c, const uint8_t* hdr, uint64_t hdrLen, bool endMark, uint8_t* out, uint64_t outCap,
                     uint64_t* outSize, hipStream_t s);
 
+// What a pipeline run takes over from the stream it belongs to.  The default is a run of independent
+// blocks: no dictionary, no ghost slot.
+struct RunMode {
+  int64_t dictBack = -1;  // >= 0: dictionary mode, first insertion this far before the first block
+  int legacy = 0;         // dictionary mode: a legacy frame (every block starts from empty tables)
+  uint32_t cont = 0, shift = 0, low0 = 0;  // dictionary mode: the previous chunk's table position (DictArgs)
+  bool ghost = false;     // the first block's B.prev is the ghost slot: upload the context's ghostIv into it
+};
+
+// the launchers' view of the context's buffers for the current plan.  A reserve can move a buffer, so this
+// runs after every reserve of the call (reserve_all; the dictionary's own reserves move only dict* buffers)
+PipeArgs pipe_args(const sz4_ctx* c, uint32_t maxChain, const uint8_t* in, uint8_t* out, uint64_t hdrLen)
+{
+  PipeArgs a{};
+  a.in = in;
+  a.blocks = c->blocks.as<Block>();
+  a.nblocks = (uint32_t)c->hBlocks.size();
+  a.segs = c->segs.as<Segment>();
+  a.nsegs = (uint32_t)c->hSegs.size();
+  a.dpSegs = c->dpSegs.as<DpSeg>();
+  a.ndp = (uint32_t)c->hDp.size();
+  a.maxDpCount = 1;
+  for (const Block& B : c->hBlocks) a.maxDpCount = std::max(a.maxDpCount, B.dpCount);
+  a.walkSegs = c->walkSegs.as<uint2>();
+  a.nwalk = (uint32_t)c->hWalk.size();
+  a.maxChain = maxChain;
+  a.iv = c->iv.as<Interval>();
+  a.ivCount = c->ivCount.as<uint32_t>();
+  a.mlen = c->mlen.as<uint32_t>();
+  a.mdist = c->mdist.as<uint16_t>();
+  a.sel = c->sel();
+  a.cost = c->cost.as<uint32_t>();
+  a.reach = c->reach.as<uint32_t>();
+  a.longFlag = c->longFlag.as<uint32_t>();
+  a.longBits = c->longBits.as<uint32_t>();
+  a.segLong = c->segLong.as<uint32_t>();
+  a.segTail = c->segTail.as<uint64_t>();
+  a.rank = c->rank.as<uint32_t>();
+  a.elemA = c->elemA();
+  a.elemB = c->elemB();
+  a.rmqUp = c->rmqUp();
+  a.rmqDown = c->rmqDown();
+  a.dpSide = c->dpSide();
+  a.dpRec = c->dpRec.as<uint4>();
+  a.segState = c->segState.as<uint4>();
+  a.lazySlots = c->lazySlots();
+  a.walkSlots = c->walkSlots();
+  a.walkState = c->walkState.as<uint4>();
+  a.tokens = c->tokens();
+  a.ntok = c->ntok.as<uint32_t>();
+  a.blockBytes = c->blockBytes.as<uint32_t>();
+  a.offsets = c->offsets.as<uint64_t>();
+  a.status = c->status.as<int>();
+  a.ldsWindow = c->ldsWindow;
+  a.out = out;
+  a.headerLen = hdrLen;
+  // optimal levels tokenize the parse's choices, greedy/lazy levels the (skip-filtered) matches
+  a.chosen = maxChain > (uint32_t)kGreedyMax ? a.sel : a.mlen;
+  return a;
+}
+
 // run the kernel pipeline over the planned blocks of the staged input `in`; frame goes to `out`.
 // finish = false: return once every kernel is enqueued (pipeline_finish collects the result)
-int run_pipeline(sz4_ctx* c, uint32_t maxChain, const uint8_t* in, const uint8_t* hdr, uint64_t hdrLen, bool endMark,
-                 uint8_t* out, uint64_t outCap, uint64_t* outSize, hipStream_t s, bool finish = true)
+int run_pipeline(sz4_ctx* c, const RunMode& mode, uint32_t maxChain, const uint8_t* in, const uint8_t* hdr, uint64_t hdrLen,
+                 bool endMark, uint8_t* out, uint64_t outCap, uint64_t* outSize, hipStream_t s, bool finish = true)
 {
   const uint32_t nb = (uint32_t)c->hBlocks.size();
   c->lastChain = maxChain;
@@ -459,38 +529,40 @@ int run_pipeline(sz4_ctx* c, uint32_t maxChain, const uint8_t* in, const uint8_t
     return c->fail(SZ4_E_DEVICE, "upload plan", e);
   c->uploadedVersion = c->planVersion;
   memcpy(c->uploadedAt, at, sizeof at);
-  if ((e = hipMemsetAsync(c->status.p, 0, 4, s)) || (e = hipMemsetAsync(c->longFlag.p, 0, nb * 4, s)))
+  const PipeArgs P = pipe_args(c, maxChain, in, out, hdrLen);
+  if ((e = hipMemsetAsync(P.status, 0, 4, s)) || (e = hipMemsetAsync(P.longFlag, 0, nb * 4, s)))
     return c->fail(SZ4_E_DEVICE, "upload plan", e);
   // ghost slot nb: the previous chunk's last block (only its intervals are read, through B.prev).  The
   // sources of these asynchronous copies live in the context: the stream path returns before they run
-  c->ghostN = c->ghost ? (uint32_t)c->ghostIv.size() : 0u;
-  if ((c->ghostN && (e = hipMemcpyAsync(c->iv.as<Interval>() + (uint64_t)nb * kMaxIv, c->ghostIv.data(),
-                                        c->ghostN * sizeof(Interval), hipMemcpyHostToDevice, s))) ||
-      (e = hipMemcpyAsync(c->ivCount.as<uint32_t>() + nb, &c->ghostN, 4, hipMemcpyHostToDevice, s)))
+  c->ghostN = mode.ghost ? (uint32_t)c->ghostIv.size() : 0u;
+  if ((c->ghostN && (e = hipMemcpyAsync(P.iv + (uint64_t)nb * kMaxIv, c->ghostIv.data(), c->ghostN * sizeof(Interval),
+                                        hipMemcpyHostToDevice, s))) ||
+      (e = hipMemcpyAsync(P.ivCount + nb, &c->ghostN, 4, hipMemcpyHostToDevice, s)))
     return c->fail(SZ4_E_DEVICE, "upload intervals", e);
-  const uint32_t ns = (uint32_t)c->hSegs.size();
-  Block* dB = c->blocks.as<Block>();
-  Segment* dS = c->segs.as<Segment>();
-  Interval* dIv = c->iv.as<Interval>();
-  uint32_t* dIvN = c->ivCount.as<uint32_t>();
+  const bool dictMode = mode.dictBack >= 0;
 
   mark(c, 0, s);
-  if (c->dictBack < 0) launch_runs(in, dB, nb, dIv, dIvN, s);
+  if (!dictMode) launch_runs(P, s);
   mark(c, 1, s);
-  if (c->dictBack >= 0 && maxChain > 0) {
+  if (dictMode && maxChain > 0) {
     // dictionary mode (modern and legacy frames): the data-parallel match finder of sz4_dict.hip, in
     // rounds until its assumed same-letter shortcut intervals are the ones its results imply; then the
     // usual parse
     if ((e = c->dictLast.reserve(sizeof(uint32_t) << 20)) || (e = c->dictPrevH.reserve(2 * 65536)) ||
         (e = c->dictPrevX.reserve(2 * 65536)))
       return c->fail(SZ4_E_NOMEM, "dictionary tables", e);
-    auto serial = [&]() {
-      launch_dict(in, dB, nb, maxChain, (uint32_t)c->dictBack, c->dictLegacy, c->dictLast.as<uint32_t>(),
-                  c->dictPrevH.as<uint16_t>(), c->dictPrevX.as<uint16_t>(), c->dictCont, c->dictShift, c->dictLow0,
-                  c->mlen.as<uint32_t>(), c->mdist.as<uint16_t>(), c->sel(), c->longFlag.as<uint32_t>(), s);
-    };
+    DictArgs A{P};
+    A.hBlocks = c->hBlocks.data();
+    A.dictBack = (uint32_t)mode.dictBack;
+    A.cont = mode.cont;
+    A.shift = mode.shift;
+    A.low0 = mode.low0;
+    A.legacy = mode.legacy;
+    A.last = c->dictLast.as<uint32_t>();
+    A.prevH = c->dictPrevH.as<uint16_t>();
+    A.prevX = c->dictPrevX.as<uint16_t>();
     if (c->dictSerial) {
-      serial();  // A/B and tests: the reference's loop replayed in order by one wavefront
+      launch_dict(A, s);  // A/B and tests: the reference's loop replayed in order by one wavefront
     } else {
       const uint64_t staged = c->hBlocks.back().end + 64;
       uint64_t maxBlock = 0;
@@ -518,59 +590,35 @@ int run_pipeline(sz4_ctx* c, uint32_t maxChain, const uint8_t* in, const uint8_t
             return r;
         return hipSuccess;
       };
-      if ((!c->dictLegacy && (e = tables(true))) || (e = hipMemsetAsync(dIvN, 0, nb * 4, s)))
+      if ((!mode.legacy && (e = tables(true))) || (e = hipMemsetAsync(P.ivCount, 0, nb * 4, s)))
         return c->fail(SZ4_E_DEVICE, "dictionary tables", e);
-      DictArgs A{};
-      A.in = in;
-      A.dBlocks = dB;
-      A.hBlocks = c->hBlocks.data();
-      A.nb = nb;
-      A.maxChain = maxChain;
-      A.dictBack = (uint32_t)c->dictBack;
-      A.cont = c->dictCont;
-      A.shift = c->dictShift;
-      A.low0 = c->dictLow0;
-      A.legacy = c->dictLegacy;
-      A.iv = dIv;
-      A.ivCount = dIvN;
-      A.last = c->dictLast.as<uint32_t>();
-      A.prevH = c->dictPrevH.as<uint16_t>();
-      A.prevX = c->dictPrevX.as<uint16_t>();
       A.ph = c->dictPH.as<uint16_t>();
       A.pe = c->dictPE.as<uint16_t>();
       A.keysA = c->dictKeys.as<uint64_t>();
       A.keysB = c->dictKeys.as<uint64_t>() + dict_sort_keys_max();
       A.temp = c->dictTemp.p;
       A.tempBytes = c->dictTempBytes;
-      A.mlen = c->mlen.as<uint32_t>();
-      A.mdist = c->mdist.as<uint16_t>();
-      A.sel = c->sel();
-      A.longFlag = c->longFlag.as<uint32_t>();
-      A.walkSegs = c->walkSegs.as<uint2>();
-      A.nwalk = (uint32_t)c->hWalk.size();
       A.lzMasks = c->dictLz.as<uint32_t>();
-      A.lzState = c->walkState.as<uint4>();
       A.scBits = c->dictSc.as<uint64_t>();
-      A.status = c->status.as<int>();
       A.runTab = c->dictRuns.as<uint2>();
       A.runFlag = reinterpret_cast<uint32_t*>(A.runTab + (staged / 64 + 2));
       for (uint32_t round = 0;; round++) {
         A.buildRuns = round == 0;
         A.guess = round == 0 && !c->dictNoGuess;
-        if (round > 0 && ((!c->dictLegacy && (e = tables(false))) || (e = hipMemsetAsync(c->longFlag.p, 0, nb * 4, s))))
+        if (round > 0 && ((!mode.legacy && (e = tables(false))) || (e = hipMemsetAsync(P.longFlag, 0, nb * 4, s))))
           return c->fail(SZ4_E_DEVICE, "dictionary tables", e);
         if (launch_dict_parallel(A, s)) return c->fail(SZ4_E_DEVICE, "dictionary kernels");
         int st = 0;
-        if ((e = hipMemcpyAsync(&st, c->status.p, 4, hipMemcpyDeviceToHost, s)) || (e = hipStreamSynchronize(s)))
+        if ((e = hipMemcpyAsync(&st, P.status, 4, hipMemcpyDeviceToHost, s)) || (e = hipStreamSynchronize(s)))
           return c->fail(SZ4_E_DEVICE, "dictionary rounds", e);
         if (c->dictRounds != ~0u) c->dictRounds = std::max(c->dictRounds, round + 1);  // sticky over the call's chunks
         if (!(st & (kStPrepRound | kStInvariant))) break;
-        if ((e = hipMemsetAsync(c->status.p, 0, 4, s))) return c->fail(SZ4_E_DEVICE, "dictionary rounds", e);
+        if ((e = hipMemsetAsync(P.status, 0, 4, s))) return c->fail(SZ4_E_DEVICE, "dictionary rounds", e);
         // every round settles a longer prefix, so this is a safety net, not a path: the in-order replay
         if ((st & kStInvariant) || round + 1 >= (c->dictMaxRounds ? c->dictMaxRounds : dict_round_cap(maxBlock))) {
-          if ((!c->dictLegacy && (e = tables(false))) || (e = hipMemsetAsync(c->longFlag.p, 0, nb * 4, s)))
+          if ((!mode.legacy && (e = tables(false))) || (e = hipMemsetAsync(P.longFlag, 0, nb * 4, s)))
             return c->fail(SZ4_E_DEVICE, "dictionary tables", e);
-          serial();
+          launch_dict(A, s);
           c->dictRounds = ~0u;
           break;
         }
@@ -583,60 +631,37 @@ int run_pipeline(sz4_ctx* c, uint32_t maxChain, const uint8_t* in, const uint8_t
   }
   // greedy/lazy levels: k_lazy_check verifies the shortcut intervals k_runs assumed; a corrected block
   // needs another sort/find/walk round (each round checks a longer prefix of it)
-  for (uint32_t round = 0; c->dictBack < 0; round++) {
+  for (uint32_t round = 0; !dictMode; round++) {
     if (maxChain > 0) {
       // k_find_sorted writes every target (shortcut-interval targets "unresolved", for pass 2); its
       // marker bits are OR-ed in
-      if ((e = hipMemsetAsync(c->longBits.p, 0, c->hBlocks.back().end / 8 + 8, s)))
+      if ((e = hipMemsetAsync(P.longBits, 0, c->hBlocks.back().end / 8 + 8, s)))
         return c->fail(SZ4_E_DEVICE, "clear matches", e);
     }
     mark(c, 2, s);
-    if (maxChain > 0)
-      launch_find(1, in, dS, ns, dB, dIv, dIvN, c->elemB(), c->elemA(), c->rank.as<uint32_t>(), maxChain,
-                  c->mlen.as<uint32_t>(), c->mdist.as<uint16_t>(), 0, c->longBits.as<uint32_t>(), c->segLong.as<uint32_t>(),
-                  nullptr, nullptr, nullptr, nullptr, c->ldsWindow, s);
+    if (maxChain > 0) launch_find(1, P, s);
     mark(c, 3, s);
     if (c->stopAfter == 2) return hipStreamSynchronize(s) == hipSuccess ? SZ4_OK : c->fail(SZ4_E_DEVICE, "pipeline");
-    if (maxChain > 0)
-      launch_find(2, in, dS, ns, dB, dIv, dIvN, c->elemB(), c->elemA(), c->rank.as<uint32_t>(), maxChain,
-                  c->mlen.as<uint32_t>(), c->mdist.as<uint16_t>(), 0, c->longBits.as<uint32_t>(), c->segLong.as<uint32_t>(),
-                  c->longFlag.as<uint32_t>(), c->cost.as<uint32_t>(), c->reach.as<uint32_t>(), c->segTail.as<uint64_t>(),
-                  c->ldsWindow, s);
+    if (maxChain > 0) launch_find(2, P, s);
     mark(c, 4, s);
     if (c->stopAfter == 3) return hipStreamSynchronize(s) == hipSuccess ? SZ4_OK : c->fail(SZ4_E_DEVICE, "pipeline");
-    launch_prep(in, dB, nb, dIv, dIvN, maxChain, c->mlen.as<uint32_t>(), c->mdist.as<uint16_t>(), 0, c->sel(),
-                c->longFlag.as<uint32_t>(), c->status.as<int>(), s);
+    launch_prep(P, s);
     if (maxChain == 0 || maxChain > (uint32_t)kLazyMax) break;
     // greedy/lazy: the reference's skip bookkeeping in parallel over the assumed shortcut intervals, which
-    // k_lazy_check / k_lazy_correct then compare with the ones the searches imply (blockBytes is free until
-    // the token walk: it holds each block's first difference)
-    launch_lazy(in, dB, nb, c->walkSegs.as<uint2>(), (uint32_t)c->hWalk.size(), dIv, dIvN, c->longFlag.as<uint32_t>(),
-                c->mlen.as<uint32_t>(), c->mdist.as<uint16_t>(), 0, c->lazySlots(), c->walkState.as<uint4>(),
-                c->blockBytes.as<uint32_t>(), c->status.as<int>(), s);
+    // k_lazy_check / k_lazy_correct then compare with the ones the searches imply
+    launch_lazy(P, s);
     int st = 0;
-    if ((e = hipMemcpyAsync(&st, c->status.p, 4, hipMemcpyDeviceToHost, s)) || (e = hipStreamSynchronize(s)))
+    if ((e = hipMemcpyAsync(&st, P.status, 4, hipMemcpyDeviceToHost, s)) || (e = hipStreamSynchronize(s)))
       return c->fail(SZ4_E_DEVICE, "prep", e);
     if (!(st & 2)) break;
     if (round > 2 * kMaxIv + 2) return c->fail(SZ4_E_DEVICE, "shortcut intervals did not settle");
-    if ((e = hipMemsetAsync(c->status.p, 0, 4, s)) || (e = hipMemsetAsync(c->longFlag.p, 0, nb * 4, s)))
+    if ((e = hipMemsetAsync(P.status, 0, 4, s)) || (e = hipMemsetAsync(P.longFlag, 0, nb * 4, s)))
       return c->fail(SZ4_E_DEVICE, "prep", e);
   }
-  uint32_t maxDpCount = 1;
-  for (const Block& B : c->hBlocks) maxDpCount = std::max(maxDpCount, B.dpCount);
-  launch_parse(in, dB, nb, c->dpSegs.as<DpSeg>(), (uint32_t)c->hDp.size(), maxDpCount, dIvN, maxChain, c->mlen.as<uint32_t>(),
-               c->mdist.as<uint16_t>(), 0, c->cost.as<uint32_t>(), c->sel(), c->reach.as<uint32_t>(),
-               c->segState.as<uint4>(), c->longFlag.as<uint32_t>(), c->rmqUp(), c->rmqDown(),
-               c->dpSide(), c->dpRec.as<uint4>(),
-               c->status.as<int>(), s);
+  launch_parse(P, s);
   mark(c, 5, s);
   if (c->stopAfter == 4) return hipStreamSynchronize(s) == hipSuccess ? SZ4_OK : c->fail(SZ4_E_DEVICE, "pipeline");
-  // optimal levels tokenize the parse's choices, greedy/lazy levels the (skip-filtered) matches
-  const uint32_t* chosen = maxChain > (uint32_t)kGreedyMax ? c->sel() : c->mlen.as<uint32_t>();
-  // the parse's reach array is free by now: it holds each block's concatenated match positions
-  launch_emit(in, dB, nb, c->walkSegs.as<uint2>(), (uint32_t)c->hWalk.size(), maxChain, chosen, c->mdist.as<uint16_t>(), 0,
-              c->walkSlots(), c->walkState.as<uint4>(), c->reach.as<uint32_t>(), c->tokens(),
-              c->ntok.as<uint32_t>(), c->blockBytes.as<uint32_t>(), c->offsets.as<uint64_t>(), out, hdrLen,
-              c->status.as<int>(), s);
+  launch_emit(P, s);
   mark(c, 6, s);
   if ((e = hipGetLastError())) return c->fail(SZ4_E_DEVICE, "kernel launch", e);
   c->lastBlocks = nb;
@@ -948,19 +973,12 @@ void plan_chunk(sz4_ctx* c, const StreamChunk& ch, int legacy, bool dictMode)
   const uint64_t bs = legacy ? kBlockMaxLegacy : kBlockMax;
   c->hBlocks.clear();
   for (uint64_t st = 0; st < ch.n; st += bs) {
-    Block B{};
-    B.start = ch.pre + st;
-    B.end = ch.pre + std::min(st + bs, ch.n);
-    if (legacy || (st == 0 && ch.first)) {
-      B.low = B.start;
-      B.cut = kNone;
-      B.prev = kNoBlock;
-    } else {
+    Block B = independent_block(ch.pre + st, ch.pre + std::min(st + bs, ch.n), legacy ? kBlkLegacy : 0);
+    if (!legacy && !(st == 0 && ch.first)) {
       B.low = B.start - kWindow;
       B.cut = B.start - kTailNoMatch;  // re-inserted by the lookback of the next block
       B.prev = st == 0 ? kNoBlock - 1 : (uint32_t)c->hBlocks.size() - 1;  // first: the ghost slot, below
     }
-    B.flags = legacy ? kBlkLegacy : 0;
     c->hBlocks.push_back(B);
   }
   const uint32_t nb = (uint32_t)c->hBlocks.size();
@@ -1004,10 +1022,9 @@ int stream_compress_body(sz4_ctx* c, sz4_get_bytes get, sz4_send_bytes send, uin
   if (bad) return c->fail(SZ4_E_ARG, "getBytes returned more bytes than asked for");
   // dictionary: the staged stream starts with the reference's data buffer, a 65535-byte prefix (the
   // dictionary's last bytes, zero-padded in front) (smallz4.h:554-571)
-  c->dictBack = dictMode ? (int64_t)std::min<uint64_t>(dictLen, kWindow) : -1;
-  c->dictLegacy = legacy;
-  c->dictCont = 0;
-  c->ghost = false;
+  RunMode mode;
+  mode.dictBack = dictMode ? (int64_t)std::min<uint64_t>(dictLen, kWindow) : -1;
+  mode.legacy = legacy;
   ch[0].pre = dictMode && ch[0].n ? kWindow : 0;
   ch[0].first = true;
   if (ch[0].n) {
@@ -1051,13 +1068,13 @@ int stream_compress_body(sz4_ctx* c, sz4_get_bytes get, sz4_send_bytes send, uin
   auto compute = [&](uint32_t k) -> int {
     const uint32_t sl = k & 1;
     const StreamChunk& x = ch[sl];
-    c->ghost = !legacy && !x.first && !dictMode;
+    mode.ghost = !legacy && !x.first && !dictMode;
     plan_chunk(c, x, legacy, dictMode);
     if (int r = reserve_all(c, x.pre + x.n + kPad)) return r;
     if ((e = hipStreamWaitEvent(c->stream, c->evUp[sl], 0))) return c->fail(SZ4_E_DEVICE, "chunk", e);
     uint64_t unused = 0;
-    if (int r = run_pipeline(c, maxChain, c->stagedS[sl].as<uint8_t>(), nullptr, 0, false, c->chunkOut[sl].as<uint8_t>(),
-                             c->chunkOut[sl].cap, &unused, c->stream, false))
+    if (int r = run_pipeline(c, mode, maxChain, c->stagedS[sl].as<uint8_t>(), nullptr, 0, false,
+                             c->chunkOut[sl].as<uint8_t>(), c->chunkOut[sl].cap, &unused, c->stream, false))
       return r;
     if ((e = hipEventRecord(c->evDone[sl], c->stream))) return c->fail(SZ4_E_DEVICE, "chunk", e);
     return SZ4_OK;
@@ -1090,9 +1107,9 @@ int stream_compress_body(sz4_ctx* c, sz4_get_bytes get, sz4_send_bytes send, uin
       }
     }
     if (dictMode) {
-      c->dictCont = legacy ? 0u : 1u;
-      c->dictShift = (uint32_t)shift;
-      c->dictLow0 = (uint32_t)(x.nextPre() - kWindow);
+      mode.cont = legacy ? 0u : 1u;
+      mode.shift = (uint32_t)shift;
+      mode.low0 = (uint32_t)(x.nextPre() - kWindow);
     }
     return SZ4_OK;
   };
@@ -1370,14 +1387,7 @@ int batch_run(sz4_ctx* c, const std::vector<uint64_t>& idx, const void* const* p
     const uint64_t n = sizes[idx[k]];
     if (planes) typed[k] = BatchTyped{(uint64_t)(uintptr_t)ptrs[idx[k]], at, (uint32_t)n, elems[idx[k]]};
     else items[k] = BatchItem{(uint64_t)(uintptr_t)ptrs[idx[k]], at, n};
-    Block B{};
-    B.start = at;
-    B.end = at + n;
-    B.low = at;
-    B.cut = kNone;
-    B.prev = kNoBlock;
-    B.flags = 0;
-    c->hBlocks.push_back(B);
+    c->hBlocks.push_back(independent_block(at, at + n));
     at += batch_stride(n);
   }
   finish_plan(c);
@@ -1400,7 +1410,7 @@ int batch_run(sz4_ctx* c, const std::vector<uint64_t>& idx, const void* const* p
   else launch_batch_gather(c->batchItems.as<BatchItem>(), nb, c->staged.as<uint8_t>(), stagedBytes, s);
   if (c->timing) hipEventRecord(c->evGather[1], s);
   uint64_t size = 0;
-  if (int r = run_pipeline(c, maxChain, c->staged.as<uint8_t>(), nullptr, 0, false, out, outCap, &size, s)) return r;
+  if (int r = run_pipeline(c, RunMode{}, maxChain, c->staged.as<uint8_t>(), nullptr, 0, false, out, outCap, &size, s)) return r;
   if (c->timing) {
     float ms = 0;
     if (hipEventElapsedTime(&ms, c->evGather[0], c->evGather[1]) == hipSuccess) c->gatherMs += ms;
@@ -1615,9 +1625,7 @@ int sz4_compress_blocks_device(sz4_ctx* c, const void* d_in, uint64_t n, uint32_
   if (out_cap < sz4_bound(n, block_size)) return c->fail(SZ4_E_CAPACITY, "out_cap < sz4_bound(n, block_size)");
   DeviceGuard guard(c->device);
   try {
-  c->ghost = false;
   hipStream_t s = (hipStream_t)stream;
-  c->dictBack = -1;
   uint8_t hdr[8];
   uint64_t hl = 0;
   bool endMark = true;
@@ -1665,16 +1673,8 @@ int sz4_compress_blocks_device(sz4_ctx* c, const void* d_in, uint64_t n, uint32_
     const bool firstPiece = off == 0, lastPiece = off + len == n;
     if (c->planN != len || c->planBS != block_size) {
       c->hBlocks.clear();
-      for (uint64_t st = 0; st < len; st += block_size) {
-        Block B{};
-        B.start = st;
-        B.end = std::min<uint64_t>(st + block_size, len);
-        B.low = st;
-        B.cut = kNone;
-        B.prev = kNoBlock;
-        B.flags = 0;
-        c->hBlocks.push_back(B);
-      }
+      for (uint64_t st = 0; st < len; st += block_size)
+        c->hBlocks.push_back(independent_block(st, std::min<uint64_t>(st + block_size, len)));
       finish_plan(c);
       c->planN = len;
       c->planBS = block_size;
@@ -1696,8 +1696,8 @@ int sz4_compress_blocks_device(sz4_ctx* c, const void* d_in, uint64_t n, uint32_
       return c->fail(SZ4_E_DEVICE, "stage input", e);
     if ((e = hipMemsetAsync(c->staged.as<uint8_t>() + len, 0, kPad, s))) return c->fail(SZ4_E_DEVICE, "stage pad", e);
     uint64_t size = 0;
-    if (int r = run_pipeline(c, max_chain, c->staged.as<uint8_t>(), hdr, firstPiece ? hl : 0, lastPiece && endMark,
-                             (uint8_t*)d_out + pos, out_cap - pos, &size, s))
+    if (int r = run_pipeline(c, RunMode{}, max_chain, c->staged.as<uint8_t>(), hdr, firstPiece ? hl : 0,
+                             lastPiece && endMark, (uint8_t*)d_out + pos, out_cap - pos, &size, s))
       return r;
     pos += size;
     for (int i = 0; i < kStages; i++) stageSum[i] += c->stageMs[i];
@@ -1765,8 +1765,6 @@ static int compress_batch(sz4_ctx* c, const void* const* in_ptrs, const uint32_t
   if (bound && !d_out) return c->fail(SZ4_E_ARG, "bad argument");
   DeviceGuard guard(c->device);
   try {
-  c->ghost = false;
-  c->dictBack = -1;
   hipStream_t s = (hipStream_t)stream;
   // per item sizes for sz4_last_block_sizes (0 for an empty item), filled piece by piece
   c->hostBytes.assign(count, 0u);

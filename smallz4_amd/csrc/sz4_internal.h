@@ -1,5 +1,6 @@
 // sz4_internal.h -- descriptors shared by the host driver (sz4_host.cpp) and the
-// gfx950 kernels (sz4_kernels.hip).  Not part of the public ABI.
+// gfx950 kernels (sz4_kernels.hip, sz4_dict.hip), and the launchers between them: the
+// compressor's take one PipeArgs (DictArgs in dictionary mode).  Not part of the public ABI.
 #pragma once
 #include <stdint.h>
 
@@ -93,94 +94,109 @@ constexpr uint32_t kTokLast = 0x80000000u;
 
 // kernels (sz4_kernels.hip)
 uint32_t find_lds_bytes();
-void launch_runs(const uint8_t* in, const Block* blocks, uint32_t nblocks, Interval* iv, uint32_t* ivCount,
-                 hipStream_t s);
-// pass 1 = k_find_sorted (each segment sorted first inside it: compact = sorted slot arrays, scratch = sort
-// buffer, rank written), pass 2 = k_find_big / k_find_long9 / k_find (long matches and shortcut intervals)
-// scratch: per-slot words free after the sort (the skip pointers of k_find_long9); longBits: one bit per
-// position marked for pass 2 (searched, not a shortcut interval); segLong: per segment, any such target;
-// specLen/specDist: per position words free before the parse (k_find_big's left-maximal results, then the
-// speculative carries of pass-2 piece heads); segTail: per segment, k_find_big's state after its last target
-void launch_find(int pass, const uint8_t* in, const Segment* segs, uint32_t nsegs, const Block* blocks,
-                 const Interval* iv, const uint32_t* ivCount, uint2* compact, uint2* scratch,
-                 uint32_t* rank, uint32_t maxChain, uint32_t* mlen, uint16_t* mdist, uint64_t matchBase,
-                 uint32_t* longBits, uint32_t* segLong, uint32_t* longFlag, uint32_t* specLen, uint32_t* specDist,
-                 uint64_t* segTail, bool ldsWindow, hipStream_t s);
-// dictionary mode: one wavefront replays the reference's match loop (dictBack = first insertion offset
-// before the first block); last: 2^20 u32, prevH / prevX: 65536 u16 each -- the reference's tables,
-// kept in HBM between the chunks of one stream.  cont: the first block continues the stream of the
-// previous launch, whose staged positions were `shift` (a multiple of 65536) higher; low0 = its dataZero
-void launch_dict(const uint8_t* in, const Block* blocks, uint32_t nblocks, uint32_t maxChain, uint32_t dictBack, int legacy,
-                 uint32_t* last, uint16_t* prevH, uint16_t* prevX, uint32_t cont, uint32_t shift, uint32_t low0,
-                 uint32_t* mlen, uint16_t* mdist, uint32_t* sel, uint32_t* longFlag, hipStream_t s);
-// dictionary mode on the whole GPU (sz4_dict.hip), modern and legacy frames: hBlocks is the host copy of
-// the plan, walkSegs the token walk's sub-segments; ph / pe: one u16 per staged position; keysA / keysB:
-// dict_sort_keys_max() u64 each; temp: dict_sort_temp_bytes(); scBits: dict_sc_bits_bytes().  iv /
-// ivCount: the assumed same-letter shortcut intervals per block (kMaxIv each); the launch replaces them
-// with the ones its results imply and raises kStPrepRound in *status when they differ (then the chunk
-// is run again from its saved tables).  Returns 0, or -1 on a launch failure
+// The buffers of one pipeline run, as every compressor launcher takes them: the host driver fills one
+// PipeArgs per run (pipe_args in sz4_host.cpp) once all of the run's buffers are reserved.  Arrays "per
+// position" are indexed by the absolute staged position, like Block's fields.
+struct PipeArgs {
+  const uint8_t* in;        // the staged input (padded: the kernels read 4-byte windows past the last block)
+  const Block* blocks;      // the plan's blocks
+  uint32_t nblocks;
+  const Segment* segs;      // the match search's segments
+  uint32_t nsegs;
+  const DpSeg* dpSegs;      // the parse's segments
+  uint32_t ndp;
+  uint32_t maxDpCount;      // the largest dpCount of the run's blocks (sizes k_dp_fix<false>'s LDS tables)
+  const uint2* walkSegs;    // the token walk's sub-segments (block, index in the block)
+  uint32_t nwalk;
+  uint32_t maxChain;        // the reference's maxChainLength (<= kGreedyMax greedy, <= kLazyMax lazy, else optimal)
+  Interval* iv;             // the same-letter shortcut intervals, kMaxIv per block (+ the ghost slot nblocks)
+  uint32_t* ivCount;        // ... and how many each block has
+  uint32_t* mlen;           // per position: the match length found (0: none)
+  uint16_t* mdist;          // per position: its distance
+  uint32_t* sel;            // per position: the parse's choice (k_prep writes the block tails)
+  // cost / reach, per position, belong to the parse; before it they are pass 2's specLen / specDist
+  // (k_find_big's left-maximal results, then the speculative carries of pass-2 piece heads), and after it
+  // reach is the token walk's posList (each block's concatenated match positions and per-sub-segment records)
+  uint32_t* cost;
+  uint32_t* reach;
+  uint32_t* longFlag;       // per block: kFlagRmq / kFlagRun, set by the match finders
+  uint32_t* longBits;       // one bit per position marked for pass 2 (searched, not a shortcut interval)
+  uint32_t* segLong;        // per segment: any such target
+  uint64_t* segTail;        // per segment: k_find_big's state after its last target
+  uint32_t* rank;           // per target: its rank in the segment's sort (written by pass 1)
+  // the two halves of the sort elements: pass 1 sorts in elemA and leaves the sorted slot arrays in elemB;
+  // elemA's per-slot words are free after the sort (the skip pointers of k_find_long9)
+  uint2* elemA;
+  uint2* elemB;
+  uint32_t* rmqUp;          // the parse's range minima, (staged + nblocks + 8) words each
+  uint32_t* rmqDown;
+  uint2* dpSide;            // k_dp_fix<true>'s saved speculative values: dp_side_positions() per DpSeg
+  uint4* dpRec;             // ... and one record per DpSeg
+  uint4* segState;          // per DpSeg: the speculative parse's boundary state
+  uint32_t* lazySlots;      // greedy/lazy replay: lazy_slots_per_walk() words per walk sub-segment
+  uint32_t* walkSlots;      // token walk: 2 * kWalkCap match positions per walk sub-segment
+  uint4* walkState;         // per walk sub-segment: the state of the replay, then of the token walk
+  Token* tokens;            // the frame's tokens (Block::tokOff)
+  uint32_t* ntok;           // per block: its token count
+  uint32_t* blockBytes;     // per block: its size word; until the token walk, the lazy check's first difference
+  uint64_t* offsets;        // per block: its offset in the frame body (slot nblocks: the body's size)
+  int* status;              // the device status word (kSt*)
+  bool ldsWindow;           // every segment's window fits the finders' LDS: the _lds kernels take the launch
+  // launch_emit alone:
+  uint8_t* out;             // the frame
+  uint64_t headerLen;       // bytes the host writes in front of the first block
+  const uint32_t* chosen;   // the lengths the token walk follows: sel (optimal levels) or mlen (greedy/lazy)
+};
+void launch_runs(const PipeArgs& a, hipStream_t s);
+// pass 1 = k_find_sorted (each segment sorted first inside it, rank written), pass 2 = k_find_big /
+// k_find_long9 / k_find (long matches and shortcut intervals)
+void launch_find(int pass, const PipeArgs& a, hipStream_t s);
+// dictionary mode (sz4_dict.hip and the in-order replay k_dict_matches), modern and legacy frames.
+// dictBack = first insertion offset before the first block; last: 2^20 u32, prevH / prevX: 65536 u16
+// each -- the reference's tables, kept in HBM between the chunks of one stream.  cont: the first block
+// continues the stream of the previous launch, whose staged positions were `shift` (a multiple of 65536)
+// higher; low0 = its dataZero.  hBlocks is the host copy of the plan; ph / pe: one u16 per staged
+// position; keysA / keysB: dict_sort_keys_max() u64 each; temp: dict_sort_temp_bytes(); scBits:
+// dict_sc_bits_bytes().  iv / ivCount: the assumed same-letter shortcut intervals per block; the parallel
+// launch replaces them with the ones its results imply and raises kStPrepRound in *status when they
+// differ (then the chunk is run again from its saved tables)
 constexpr uint64_t kBlockMaxDict = 4ull << 20;     // MaxBlockSize (smallz4.h:124)
 constexpr uint64_t kBlockMaxLegacy = 8ull << 20;   // MaxBlockSizeLegacy (smallz4.h:125)
-struct DictArgs {
-  const uint8_t* in;
-  const Block* dBlocks;
+struct DictArgs : PipeArgs {
   const Block* hBlocks;
-  uint32_t nb, maxChain, dictBack, cont, shift, low0;
+  uint32_t dictBack, cont, shift, low0;
   int legacy;
-  Interval* iv;
-  uint32_t* ivCount;
   uint32_t* last;
   uint16_t *prevH, *prevX, *ph, *pe;
   uint64_t *keysA, *keysB;
   void* temp;
   uint64_t tempBytes;
-  uint32_t* mlen;
-  uint16_t* mdist;
-  uint32_t *sel, *longFlag;
-  const uint2* walkSegs;
-  uint32_t nwalk;
-  uint32_t* lzMasks;
-  uint4* lzState;
+  uint32_t* lzMasks;  // greedy/lazy levels: dict_lz_mask_bytes_per_walk() bytes per walk sub-segment (with walkState)
   uint64_t* scBits;
-  int* status;
   uint2* runTab;      // runs covering whole 64-byte chunks: dict_run_table_bytes(staged) with runFlag
   uint32_t* runFlag;
   bool buildRuns;     // the first round of a chunk builds the table (the input does not change)
   bool guess;         // ... and appends its guess of the shortcut intervals to iv / ivCount (zeroed before)
 };
+// one wavefront replays the reference's match loop in order
+void launch_dict(const DictArgs& a, hipStream_t s);
 uint64_t dict_sort_keys_max();
 uint64_t dict_sort_temp_bytes();  // rocPRIM's scratch for dict_sort_keys_max() keys; 0 if the query failed
 uint64_t dict_sc_bits_bytes(uint32_t nb, uint64_t maxBlock);
 uint64_t dict_run_table_bytes(uint64_t staged);
 int launch_dict_parallel(const DictArgs& a, hipStream_t s);
-// greedy/lazy levels: dict_lz_mask_bytes_per_walk() bytes per token-walk sub-segment (lzMasks), one
-// uint4 per sub-segment (lzState)
 uint64_t dict_lz_mask_bytes_per_walk();
 // k_prep: the tail positions the reference never searches (lengths 0, literal choices)
-void launch_prep(const uint8_t* in, const Block* blocks, uint32_t nblocks, Interval* iv, uint32_t* ivCount, uint32_t maxChain,
-                 uint32_t* mlen, uint16_t* mdist, uint64_t matchBase, uint32_t* sel, const uint32_t* longFlag, int* status,
-                 hipStream_t s);
+void launch_prep(const PipeArgs& a, hipStream_t s);
 // greedy/lazy levels: the parallel replay of the reference's skip bookkeeping (k_lazy_walk / k_lazy_fix /
 // k_lazy_clear) over the assumed same-letter shortcut intervals, then their check (k_lazy_check /
-// k_lazy_correct: status kStPrepRound = an interval list was corrected, run sort/find/walk again);
-// slots: lazy_slots_per_walk() u32 per walk sub-segment, state: one uint4 per walk sub-segment,
-// firstBad: one u32 per block
-void launch_lazy(const uint8_t* in, const Block* blocks, uint32_t nblocks, const uint2* walkSegs, uint32_t nwalk,
-                 Interval* iv, uint32_t* ivCount, const uint32_t* longFlag, uint32_t* mlen, const uint16_t* mdist,
-                 uint64_t matchBase, uint32_t* slots, uint4* state, uint32_t* firstBad, int* status, hipStream_t s);
+// k_lazy_correct: status kStPrepRound = an interval list was corrected, run sort/find/walk again)
+void launch_lazy(const PipeArgs& a, hipStream_t s);
 uint32_t lazy_slots_per_walk();
-// maxDpCount: the largest dpCount of the launch's blocks (sizes k_dp_fix<false>'s LDS tables)
-void launch_parse(const uint8_t* in, const Block* blocks, uint32_t nblocks, const DpSeg* dpSegs, uint32_t ndp,
-                  uint32_t maxDpCount, const uint32_t* ivCount, uint32_t maxChain, uint32_t* mlen, const uint16_t* mdist,
-                  uint64_t matchBase, uint32_t* cost, uint32_t* sel, uint32_t* reach, uint4* segState,
-                  const uint32_t* longFlag, uint32_t* rmqUp, uint32_t* rmqDown, uint2* dpSide, uint4* dpRec, int* status,
-                  hipStream_t s);
-// k_dp_fix<true>'s saved speculative values: dp_side_positions() uint2 per DpSeg, and one uint4 record per DpSeg
+void launch_parse(const PipeArgs& a, hipStream_t s);
 uint32_t dp_side_positions();
-void launch_emit(const uint8_t* in, const Block* blocks, uint32_t nblocks, const uint2* walkSegs, uint32_t nwalk,
-                 uint32_t maxChain, const uint32_t* chosen, const uint16_t* mdist, uint64_t matchBase, uint32_t* walkSlots,
-                 uint4* walkState, uint32_t* posList, Token* tokens, uint32_t* ntok, uint32_t* blockBytes,
-                 uint64_t* offsets, uint8_t* out, uint64_t headerLen, int* status, hipStream_t s);
+// the token walk over a.chosen, the tokens, the block sizes and the frame body at a.out + a.headerLen
+void launch_emit(const PipeArgs& a, hipStream_t s);
 
 // decoder (sz4_unlz4.hip): one block of an LZ4 frame
 struct UnBlock {

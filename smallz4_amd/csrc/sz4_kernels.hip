@@ -924,7 +924,7 @@ template <bool kLds>
 __device__ __forceinline__ void find_sorted_body(const uint8_t* __restrict__ in, const Segment* __restrict__ segs,
                                 const Block* __restrict__ blocks, const Interval* __restrict__ ivAll,
                                 const uint32_t* __restrict__ ivCount, uint2* compactAll, uint32_t maxChain,
-                                uint32_t* __restrict__ mlen, uint16_t* __restrict__ mdist, uint64_t matchBase,
+                                uint32_t* __restrict__ mlen, uint16_t* __restrict__ mdist,
                                 uint32_t* __restrict__ longBits, uint32_t* __restrict__ segLong, uint2* sortA,
                                 uint32_t* rankOut)
 {
@@ -1695,7 +1695,7 @@ __device__ __forceinline__ void find_sorted_body(const uint8_t* __restrict__ in,
       const bool in = i < tn;
       const uint32_t v = in ? otile[i] : 0u;
       const uint32_t len = v >> 16;
-      const uint64_t idx = S.s0 + t0 + i - matchBase;
+      const uint64_t idx = S.s0 + t0 + i;
       if (in) {
         mlen[idx] = len >= kOutUnsearched ? kLongMatch : len;
         mdist[idx] = (uint16_t)(v & 0xFFFFu);
@@ -1703,7 +1703,7 @@ __device__ __forceinline__ void find_sorted_body(const uint8_t* __restrict__ in,
       // marker bits of long pass-1 targets (-9): 64 consecutive positions per wave
       const uint64_t m = __ballot(in && unlimited && len == kOutLong);
       if (m && lane == 0) {
-        const uint64_t b0 = S.s0 + t0 + (i0 + (tid & ~63u)) - matchBase;
+        const uint64_t b0 = S.s0 + t0 + (i0 + (tid & ~63u));
         const uint32_t sh = (uint32_t)(b0 & 31);
         uint32_t* w = longBits + (b0 >> 5);
         const uint64_t lo = m << sh;  // bits b0 .. b0 + 63 over words w[0..2]
@@ -1735,20 +1735,20 @@ __device__ __forceinline__ void find_sorted_body(const uint8_t* __restrict__ in,
 __global__ __launch_bounds__(kFindThreads, 2) __attribute__((amdgpu_num_sgpr(80))) void k_find_sorted_lds(const uint8_t* __restrict__ in, const Segment* __restrict__ segs,
                                 const Block* __restrict__ blocks, const Interval* __restrict__ ivAll,
                                 const uint32_t* __restrict__ ivCount, uint2* compactAll, uint32_t maxChain,
-                                uint32_t* __restrict__ mlen, uint16_t* __restrict__ mdist, uint64_t matchBase,
+                                uint32_t* __restrict__ mlen, uint16_t* __restrict__ mdist,
                                 uint32_t* __restrict__ longBits, uint32_t* __restrict__ segLong, uint2* sortA,
                                 uint32_t* rankOut)
 {
-  find_sorted_body<true>(in, segs, blocks, ivAll, ivCount, compactAll, maxChain, mlen, mdist, matchBase, longBits, segLong, sortA, rankOut);
+  find_sorted_body<true>(in, segs, blocks, ivAll, ivCount, compactAll, maxChain, mlen, mdist, longBits, segLong, sortA, rankOut);
 }
 __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8), amdgpu_num_sgpr(80))) void k_find_sorted_hbm(const uint8_t* __restrict__ in, const Segment* __restrict__ segs,
                                 const Block* __restrict__ blocks, const Interval* __restrict__ ivAll,
                                 const uint32_t* __restrict__ ivCount, uint2* compactAll, uint32_t maxChain,
-                                uint32_t* __restrict__ mlen, uint16_t* __restrict__ mdist, uint64_t matchBase,
+                                uint32_t* __restrict__ mlen, uint16_t* __restrict__ mdist,
                                 uint32_t* __restrict__ longBits, uint32_t* __restrict__ segLong, uint2* sortA,
                                 uint32_t* rankOut)
 {
-  find_sorted_body<false>(in, segs, blocks, ivAll, ivCount, compactAll, maxChain, mlen, mdist, matchBase, longBits, segLong, sortA, rankOut);
+  find_sorted_body<false>(in, segs, blocks, ivAll, ivCount, compactAll, maxChain, mlen, mdist, longBits, segLong, sortA, rankOut);
 }
 
 // (1: two workgroups per CU when the window fits LDS -- <= 64 VGPRs, <= 80 SGPRs)
@@ -1758,7 +1758,7 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
                                                        const uint32_t* __restrict__ ivCount, const uint2* __restrict__ compactAll,
                                                        const uint32_t* __restrict__ rankAll, uint32_t maxChain,
                                                        uint32_t* __restrict__ mlen, uint16_t* __restrict__ mdist,
-                                                       uint64_t matchBase, uint32_t* __restrict__ longFlag,
+                                                       uint32_t* __restrict__ longFlag,
                                                        const uint32_t* __restrict__ segLong)
 {
   extern __shared__ __attribute__((aligned(16))) uint32_t win[];
@@ -1822,7 +1822,7 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
     if (first >= nTargets) break;
     const uint32_t cnt = nTargets - first < 64 ? nTargets - first : 64;
     // pass 2: only targets pass 1 left marked (long matches, shortcut intervals) are searched here
-    const uint64_t myIdx = S.s0 + first + lane - matchBase;
+    const uint64_t myIdx = S.s0 + first + lane;
     const uint32_t pass1Len = lane < cnt ? mlen[myIdx] : 0u;
     const uint32_t pass1Dist = lane < cnt ? (uint32_t)mdist[myIdx] : 0u;
     if (__ballot(pass1Len == kLongMatch) == 0) continue;
@@ -2134,7 +2134,7 @@ __device__ __forceinline__ void find_long9_body(const uint8_t* __restrict__ in, 
                                                              uint2* __restrict__ skipAll, const uint32_t* __restrict__ rankAll,
                                                              const uint32_t* __restrict__ longBits, const uint32_t* __restrict__ segLong,
                                                              uint32_t* __restrict__ mlen, uint16_t* __restrict__ mdist,
-                                                             uint64_t matchBase, uint32_t* __restrict__ longFlag,
+                                                             uint32_t* __restrict__ longFlag,
                                                              uint32_t* __restrict__ specLen, uint32_t* __restrict__ specDist,
                                                              int fixMode)
 {
@@ -2165,11 +2165,11 @@ __device__ __forceinline__ void find_long9_body(const uint8_t* __restrict__ in, 
     bool any = false;
     if (segLong[blockIdx.x] != 0u) {
       for (uint64_t q0 = S.s0 + kPiece * (1u + tid); q0 < S.s1; q0 += (uint64_t)kPiece * kFindThreads) {
-        const uint64_t i0 = q0 - matchBase, i1 = q0 - 1 - matchBase;
+        const uint64_t i0 = q0, i1 = q0 - 1;
         if (!((longBits[i0 >> 5] >> (i0 & 31)) & 1u) || !((longBits[i1 >> 5] >> (i1 & 31)) & 1u)) continue;
-        const uint32_t sd = specDist[q0 - matchBase];
+        const uint32_t sd = specDist[q0];
         if (sd == 0u) continue;
-        if (mlen[q0 - 1 - matchBase] == specLen[q0 - matchBase] && mdist[q0 - 1 - matchBase] == sd) continue;
+        if (mlen[q0 - 1] == specLen[q0] && mdist[q0 - 1] == sd) continue;
         any = true;
       }
     }
@@ -2226,7 +2226,7 @@ __device__ __forceinline__ void find_long9_body(const uint8_t* __restrict__ in, 
     return src.ld4(q - 1) & 0xFFu;
   };
   auto long_bit = [&](uint64_t q) -> bool {
-    const uint64_t idx = q - matchBase;
+    const uint64_t idx = q;
     return (longBits[idx >> 5] >> (idx & 31)) & 1u;
   };
 
@@ -2360,7 +2360,7 @@ __device__ __forceinline__ void find_long9_body(const uint8_t* __restrict__ in, 
     const bool prune = exact && cut == kNone && (carryOk || cLen < 5u);
     const uint32_t pc = prune ? (src.ld4(p - 1) & 0xFFu) : 0xFFFFu;
     // pass 1's nearest candidate at its cap
-    const uint32_t seed = mdist[p - matchBase];
+    const uint32_t seed = mdist[p];
     if (seed != 0u && (bestLen < room || seed < bestDist)) {
       bool rk;
       const uint32_t rl = run_prefix(p, p - seed, room, rk);
@@ -2507,7 +2507,7 @@ __device__ __forceinline__ void find_long9_body(const uint8_t* __restrict__ in, 
     const uint64_t lim = pieceEnd < S.s1 ? pieceEnd : S.s1;
     uint64_t qEnd = q;
     while (qEnd < lim) {
-      const uint64_t qi = qEnd - matchBase;
+      const uint64_t qi = qEnd;
       const uint32_t w = longBits[qi >> 5] >> (qi & 31);  // the word's bits from qEnd on
       const uint32_t ones = (uint32_t)__builtin_ctzll(~(uint64_t)w);  // <= 32 - (qi & 31)
       qEnd += ones;
@@ -2527,8 +2527,8 @@ __device__ __forceinline__ void find_long9_body(const uint8_t* __restrict__ in, 
         const uint64_t breaks = __ballot(mine && !keeps);
         const uint32_t f = breaks ? (uint32_t)__builtin_ctzll(breaks) : spec - 1u;  // last lane taken
         if (lane <= f) {
-          mlen[q + lane - matchBase] = rL;
-          mdist[q + lane - matchBase] = (uint16_t)rD;
+          mlen[q + lane] = rL;
+          mdist[q + lane] = (uint16_t)rD;
         }
         rmqLen |= __ballot(lane <= f && rL >= kRmqLen && !(rD == 1u && rL >= kSameLetter)) != 0;
         bLen = rdlane(rL, f);
@@ -2537,8 +2537,8 @@ __device__ __forceinline__ void find_long9_body(const uint8_t* __restrict__ in, 
       } else {
         best_of(q, cLen, cDist, exact, bLen, bDist);
         if (lane == 0) {
-          mlen[q - matchBase] = bLen;
-          mdist[q - matchBase] = (uint16_t)bDist;
+          mlen[q] = bLen;
+          mdist[q] = (uint16_t)bDist;
         }
         rmqLen |= bLen >= kRmqLen && !(bDist == 1u && bLen >= kSameLetter);
         q++;
@@ -2557,10 +2557,10 @@ __device__ __forceinline__ void find_long9_body(const uint8_t* __restrict__ in, 
     if (wave != 0 || !searched) return;
     for (uint64_t q0 = S.s0 + kPiece; q0 < S.s1; q0 += kPiece) {
       if (!long_bit(q0) || !long_bit(q0 - 1)) continue;
-      const uint32_t sd = specDist[q0 - matchBase];
+      const uint32_t sd = specDist[q0];
       if (sd == 0u) continue;  // walked without a carry: exact
-      const uint32_t aLen = mlen[q0 - 1 - matchBase], aDist = mdist[q0 - 1 - matchBase];
-      if (aLen == specLen[q0 - matchBase] && aDist == sd) continue;
+      const uint32_t aLen = mlen[q0 - 1], aDist = mdist[q0 - 1];
+      if (aLen == specLen[q0] && aDist == sd) continue;
       walk_stretch(q0, aLen, aDist, true);
       SZ4_D5(if (lane_id() == 0) atomicAdd((unsigned long long*)&sz4_diag[4], 1ull);)
     }
@@ -2576,7 +2576,7 @@ __device__ __forceinline__ void find_long9_body(const uint8_t* __restrict__ in, 
     if (first >= nTargets) break;
     const uint32_t cnt = nTargets - first < 64 ? nTargets - first : 64;
     const uint64_t p = S.s0 + first + lane;
-    const uint64_t myIdx = p - matchBase;
+    const uint64_t myIdx = p;
     const uint32_t p1 = lane < cnt ? mlen[myIdx] : 0u;
     if (__ballot(p1 == kLongMatch) == 0) continue;
     const bool lg = lane < cnt && long_bit(p);
@@ -2616,8 +2616,8 @@ __device__ __forceinline__ void find_long9_body(const uint8_t* __restrict__ in, 
       uint32_t cLen = 0, cDist = 0;
       bool exact = false;
       if (q > B.start && !long_bit(q - 1) && !(niv && in_iv(iv, niv, q - 1))) {
-        cLen = mlen[q - 1 - matchBase];
-        cDist = mdist[q - 1 - matchBase];
+        cLen = mlen[q - 1];
+        cDist = mdist[q - 1];
         exact = true;
       } else if (q != S.s0 && long_bit(q - 1) && cut == kNone) {
         // a piece head inside a stretch: speculate that its predecessor's best match is the one
@@ -2635,8 +2635,8 @@ __device__ __forceinline__ void find_long9_body(const uint8_t* __restrict__ in, 
         }
       }
       if (lane == 0 && q != S.s0 && long_bit(q - 1)) {
-        specLen[q - matchBase] = cLen;
-        specDist[q - matchBase] = exact ? cDist : 0u;
+        specLen[q] = cLen;
+        specDist[q] = exact ? cDist : 0u;
       }
       walk_stretch(q, cLen, cDist, exact);
     }
@@ -2650,10 +2650,10 @@ __device__ __forceinline__ void find_long9_body(const uint8_t* __restrict__ in, 
       const Interval *__restrict__ ivAll, const uint32_t *__restrict__ ivCount,                               \
       const uint2 *__restrict__ compactAll, uint2 *__restrict__ skipAll, const uint32_t *__restrict__ rankAll, \
       const uint32_t *__restrict__ longBits, const uint32_t *__restrict__ segLong, uint32_t *__restrict__ mlen, \
-      uint16_t *__restrict__ mdist, uint64_t matchBase, uint32_t *__restrict__ longFlag,                      \
+      uint16_t *__restrict__ mdist, uint32_t *__restrict__ longFlag,                      \
       uint32_t *__restrict__ specLen, uint32_t *__restrict__ specDist, int fixMode
 #define SZ4_LONG9_PASS in, segs, blocks, ivAll, ivCount, compactAll, skipAll, rankAll, longBits, segLong, mlen, mdist, \
-                       matchBase, longFlag, specLen, specDist, fixMode
+                       longFlag, specLen, specDist, fixMode
 __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_num_sgpr(80))) void k_find_long9_lds(SZ4_LONG9_ARGS)
 {
   find_long9_body<true>(SZ4_LONG9_PASS);
@@ -2740,7 +2740,7 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
                                                            const uint2* __restrict__ compactAll, uint2* __restrict__ scratchAll,
                                                            uint32_t* __restrict__ longBits, const uint32_t* __restrict__ segLong,
                                                            uint32_t* __restrict__ mlen, uint16_t* __restrict__ mdist,
-                                                           uint64_t matchBase, uint32_t* __restrict__ lm, uint64_t* __restrict__ segTail,
+                                                           uint32_t* __restrict__ lm, uint64_t* __restrict__ segTail,
                                                            uint32_t* __restrict__ runBkt, const uint32_t* __restrict__ rankAll,
                                                            uint32_t* __restrict__ longFlag, uint32_t resolveOnly)
 {
@@ -2785,7 +2785,7 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
     // when no target here is left to this kernel (no big group, or more than fit): the last target's
     // own result when pass 1 finished it, else unknown.  Phase 3 below overwrites it.
     const uint32_t nTg = (uint32_t)(S.s1 - S.s0);
-    const uint64_t idx = S.s1 - 1 - matchBase;
+    const uint64_t idx = S.s1 - 1;
     const uint32_t ml = mlen[idx], md = mdist[idx];
     uint64_t t = 0;
     if (ml != kLongMatch) {
@@ -2815,7 +2815,7 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
   const uint32_t nTg = (uint32_t)(S.s1 - S.s0);
   const uint32_t* rank = rankAll + S.rankOff;
   auto handed = [&](uint64_t q) -> bool {  // q: a target of this segment
-    const uint64_t idx = q - matchBase;
+    const uint64_t idx = q;
     return ((longBits[idx >> 5] >> (idx & 31)) & 1u) && mlen[idx] == kLongMatch && mdist[idx] == 0u;
   };
   const uint32_t gWords = (E + 31) / 32;
@@ -2910,7 +2910,7 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
   };
   uint32_t* C = reinterpret_cast<uint32_t*>(scratchAll + S.elemOff);  // candidates: cls << 17 | rel
   uint32_t* T = C + E;                                                 // targets: rel
-  uint32_t* BK = runBkt + (S.s0 - matchBase);                          // run table: runs by next byte
+  uint32_t* BK = runBkt + S.s0;                          // run table: runs by next byte
   __syncthreads();
 
   SZ4_D6(1);
@@ -2969,7 +2969,7 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
           if (isColl) {
             const uint32_t rc = slot_pos(compact, small, s);
             C[gb - 1u - j] = rc;
-            if (is_target(S.w0 + rc)) lm[S.w0 + rc - matchBase] = j;
+            if (is_target(S.w0 + rc)) lm[S.w0 + rc] = j;
           }
           nColl += tc;
         }
@@ -2986,7 +2986,7 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
           C[ga + k] = r;
           T[ga + k] = s;
         }
-        if (inG && is_target(S.w0 + r)) lm[S.w0 + r - matchBase] = first ? k : k - 1u;
+        if (inG && is_target(S.w0 + r)) lm[S.w0 + r] = first ? k : k - 1u;
         base += tot;
       }
       if (tid == 0) {
@@ -3145,7 +3145,7 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
         const uint32_t pKey = tgt ? src.ld4(p) : 0u;
         const bool coll = tgt && pKey != gKey;  // a collision member: searched one by one, below
         const bool act = tgt && !coll;
-        const uint32_t lo = tgt ? lm[p - matchBase] : 0u;  // its piece (a collision member: its list index)
+        const uint32_t lo = tgt ? lm[p] : 0u;  // its piece (a collision member: its list index)
         if (act) SZ4_D6C(8, 1);
         uint32_t fi = 0, eiRel = 0, li = 0;
         if (act) piece(lo, fi, eiRel, li);
@@ -3302,13 +3302,13 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
         W6(23);
         if (tgt) {
           // final: pass 1 and the prefix maximum below read it as an exact target
-          const uint64_t idx = p - matchBase;
+          const uint64_t idx = p;
           const bool m = bl >= (uint32_t)kMinMatch;
           mlen[idx] = m ? bl : 0u;
           mdist[idx] = m ? (uint16_t)(pRel - bc) : (uint16_t)0;
           rmq |= m && bl >= kRmqLen && !(pRel - bc == 1u && bl >= kSameLetter);
         }
-        wave_clear_bits(longBits, p - matchBase, tgt);
+        wave_clear_bits(longBits, p, tgt);
       }
       if (__ballot(rmq) && lane == 0) atomicOr(&longFlag[S.block], kFlagRmq);
       __syncthreads();
@@ -3469,7 +3469,7 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
       }
       if (act) {
         const uint32_t bl = bestKey >> 17;
-        lm[p - matchBase] = bl >= kLongCap9 && room > kLongCap9 ? kLmUnknown << 16
+        lm[p] = bl >= kLongCap9 && room > kLongCap9 ? kLmUnknown << 16
                             : bl >= (uint32_t)kMinMatch ? (bl << 16) | (uint32_t)(pRel - (bestKey & 0x1FFFFu)) : 0u;
       }
     }
@@ -3490,7 +3490,7 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
   const uint32_t r0 = wave * span, r1 = r0 + span < nTg ? r0 + span : nTg;
   auto classify = [&](uint32_t i, uint32_t& kind, uint64_t& key) {
     // kind 0 = B, 1 = E, 2 = U
-    const uint64_t p = S.s0 + i, idx = p - matchBase;
+    const uint64_t p = S.s0 + i, idx = p;
     const uint32_t ml = mlen[idx], md = mdist[idx];
     key = 0;
     if (ml != kLongMatch) {
@@ -3576,7 +3576,7 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
       }
       )
       if (phase == 1 && inR && kind == 0u && valid) {
-        const uint64_t p = S.s0 + i, idx = p - matchBase;
+        const uint64_t p = S.s0 + i, idx = p;
         const uint32_t len = (uint32_t)(v >> 16) > i ? (uint32_t)(v >> 16) - i : 0u;
         const bool m = v != 0ull && len >= (uint32_t)kMinMatch;
         const uint32_t d = 0xFFFFu - (uint32_t)(v & 0xFFFFu);
@@ -3584,7 +3584,7 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
         mdist[idx] = m ? (uint16_t)d : (uint16_t)0;
         rmq = m && len >= kRmqLen && !(d == 1u && len >= kSameLetter);  // (a run target's exact length)
       }
-      wave_clear_bits(longBits, S.s0 + i - matchBase, phase == 1 && inR && kind == 0u && valid);
+      wave_clear_bits(longBits, S.s0 + i, phase == 1 && inR && kind == 0u && valid);
       if (__ballot(rmq) && lane == 0) atomicOr(&longFlag[S.block], kFlagRmq);
       // carry to the next 64: the last lane in range
       const uint32_t last = (r1 - i0 < 64u ? r1 - i0 : 64u) - 1u;
@@ -4085,13 +4085,11 @@ __global__ __launch_bounds__(64) void k_dict_matches(const uint8_t* __restrict__
   for (uint32_t j = 0; j < 65536; j++) prevXg[j] = prevX[j];  // carried to the next chunk
 }
 
-void launch_dict(const uint8_t* in, const Block* blocks, uint32_t nblocks, uint32_t maxChain, uint32_t dictBack, int legacy,
-                 uint32_t* last, uint16_t* prevH, uint16_t* prevX, uint32_t cont, uint32_t shift, uint32_t low0,
-                 uint32_t* mlen, uint16_t* mdist, uint32_t* sel, uint32_t* longFlag, hipStream_t s)
+void launch_dict(const DictArgs& a, hipStream_t s)
 {
-  if (nblocks)
-    hipLaunchKernelGGL(k_dict_matches, dim3(1), dim3(64), 0, s, in, blocks, nblocks, maxChain, dictBack, legacy, last, prevH,
-                       prevX, cont, shift, low0, mlen, mdist, sel, longFlag);
+  if (a.nblocks)
+    hipLaunchKernelGGL(k_dict_matches, dim3(1), dim3(64), 0, s, a.in, a.blocks, a.nblocks, a.maxChain, a.dictBack, a.legacy,
+                       a.last, a.prevH, a.prevX, a.cont, a.shift, a.low0, a.mlen, a.mdist, a.sel, a.longFlag);
 }
 
 // k_prep: the positions the reference never searches -- the last 12 of a block keep length 0, the parse's
@@ -4101,15 +4099,15 @@ void launch_dict(const uint8_t* in, const Block* blocks, uint32_t nblocks, uint3
 __global__ __launch_bounds__(64) void k_prep(const uint8_t* __restrict__ in, const Block* __restrict__ blocks,
                                              Interval* __restrict__ ivAll, uint32_t* __restrict__ ivCount,
                                              uint32_t maxChain, uint32_t* __restrict__ mlen, uint16_t* __restrict__ mdist,
-                                             uint64_t matchBase, uint32_t* __restrict__ sel, const uint32_t* __restrict__ longFlag,
+                                             uint32_t* __restrict__ sel, const uint32_t* __restrict__ longFlag,
                                              int* __restrict__ status)
 {
   const Block B = blocks[blockIdx.x];
   const uint32_t lane = threadIdx.x;
   const uint64_t n = B.end - B.start;
-  uint32_t* L = mlen + (B.start - matchBase);
-  uint16_t* D = mdist + (B.start - matchBase);
-  uint32_t* S = sel + (B.start - matchBase);
+  uint32_t* L = mlen + B.start;
+  uint16_t* D = mdist + B.start;
+  uint32_t* S = sel + B.start;
   if (maxChain == 0) return;
   const uint64_t lastSearch = n >= (uint64_t)kTailNoMatch ? n - kTailNoMatch : 0;  // inclusive, relative
 
@@ -4217,7 +4215,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_lazy_walk(const Block* __re
                                                                const uint2* __restrict__ walkSegs, uint32_t nwalk,
                                                                const Interval* __restrict__ ivAll,
                                                                const uint32_t* __restrict__ ivCount,
-                                                               const uint32_t* __restrict__ mlen, uint64_t matchBase,
+                                                               const uint32_t* __restrict__ mlen,
                                                                uint32_t* __restrict__ slotsAll, uint4* __restrict__ state)
 {
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -4232,7 +4230,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_lazy_walk(const Block* __re
   const uint32_t a = ws.y * kWalkSeg;
   const uint32_t aNext = a + kWalkSeg < n ? a + kWalkSeg : n;
   LazyWalker w;
-  w.L = mlen + (B.start - matchBase);
+  w.L = mlen + B.start;
   w.lastSearch = n - kTailNoMatch;
   w.iv = ivAll + (uint64_t)ws.x * kMaxIv;
   w.niv = ivCount[ws.x];
@@ -4373,7 +4371,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_lazy_join(const Block* __re
                                                                const uint2* __restrict__ walkSegs, uint32_t nwalk,
                                                                const Interval* __restrict__ ivAll,
                                                                const uint32_t* __restrict__ ivCount,
-                                                               const uint32_t* __restrict__ mlen, uint64_t matchBase,
+                                                               const uint32_t* __restrict__ mlen,
                                                                uint32_t* __restrict__ slotsAll, uint4* __restrict__ state)
 {
   __shared__ uint32_t specAll[kWalkWaves][kLazyCap];
@@ -4402,7 +4400,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_lazy_join(const Block* __re
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   LazyWalker w;
-  w.L = mlen + (B.start - matchBase);
+  w.L = mlen + B.start;
   w.lastSearch = n - kTailNoMatch;
   w.iv = ivAll + (uint64_t)ws.x * kMaxIv;
   w.niv = ivCount[ws.x];
@@ -4420,7 +4418,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_lazy_join(const Block* __re
 
 __global__ __launch_bounds__(64) void k_lazy_fix(const Block* __restrict__ blocks, const Interval* __restrict__ ivAll,
                                                  const uint32_t* __restrict__ ivCount, const uint32_t* __restrict__ mlen,
-                                                 uint64_t matchBase, uint32_t* __restrict__ slotsAll,
+                                                 uint32_t* __restrict__ slotsAll,
                                                  uint4* __restrict__ state, int* __restrict__ status)
 {
   __shared__ uint32_t spec[kLazyCap];  // the sub-segment's speculative searches
@@ -4430,7 +4428,7 @@ __global__ __launch_bounds__(64) void k_lazy_fix(const Block* __restrict__ block
   const uint32_t n = (uint32_t)(B.end - B.start);
   if (n < (uint32_t)kTailNoMatch || B.walkCount < 2) return;
   LazyWalker w;
-  w.L = mlen + (B.start - matchBase);
+  w.L = mlen + B.start;
   w.lastSearch = n - kTailNoMatch;
   w.iv = ivAll + (uint64_t)blockIdx.x * kMaxIv;
   w.niv = ivCount[blockIdx.x];
@@ -4536,7 +4534,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_lazy_clear(const Block* __r
                                                                 const uint2* __restrict__ walkSegs, uint32_t nwalk,
                                                                 const Interval* __restrict__ ivAll,
                                                                 const uint32_t* __restrict__ ivCount,
-                                                                uint32_t* __restrict__ mlen, uint64_t matchBase,
+                                                                uint32_t* __restrict__ mlen,
                                                                 const uint32_t* __restrict__ slotsAll,
                                                                 const uint4* __restrict__ state)
 {
@@ -4550,7 +4548,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_lazy_clear(const Block* __r
   const uint32_t n = (uint32_t)(B.end - B.start);
   if (n < (uint32_t)kTailNoMatch) return;
   const uint32_t lastSearch = n - kTailNoMatch;
-  uint32_t* L = mlen + (B.start - matchBase);
+  uint32_t* L = mlen + B.start;
   const uint32_t a = ws.y * kWalkSeg;
   const uint32_t hi = a + kWalkSeg - 1 < lastSearch ? a + kWalkSeg - 1 : lastSearch;  // inclusive
   if (a > hi) return;
@@ -4601,7 +4599,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_lazy_check(const uint8_t* _
                                                                 const uint32_t* __restrict__ ivCount,
                                                                 const uint32_t* __restrict__ longFlag,
                                                                 const uint32_t* __restrict__ mlen, const uint16_t* __restrict__ mdist,
-                                                                uint64_t matchBase, const uint32_t* __restrict__ slotsAll,
+                                                                const uint32_t* __restrict__ slotsAll,
                                                                 const uint4* __restrict__ state, uint32_t* __restrict__ firstBad)
 {
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -4615,8 +4613,8 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_lazy_check(const uint8_t* _
   const uint32_t n = (uint32_t)(B.end - B.start);
   if (n < (uint32_t)kTailNoMatch) return;
   const uint32_t lastSearch = n - kTailNoMatch;
-  const uint32_t* L = mlen + (B.start - matchBase);
-  const uint16_t* D = mdist + (B.start - matchBase);
+  const uint32_t* L = mlen + B.start;
+  const uint16_t* D = mdist + B.start;
   const uint8_t* data = in + B.start;
   const Interval* iv = ivAll + (uint64_t)ws.x * kMaxIv;
   const uint4 st = state[idx];
@@ -4656,7 +4654,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_lazy_check(const uint8_t* _
 // did), and the host asked for another round
 __global__ __launch_bounds__(64) void k_lazy_correct(const Block* __restrict__ blocks, Interval* __restrict__ ivAll,
                                                      uint32_t* __restrict__ ivCount, const uint32_t* __restrict__ mlen,
-                                                     uint64_t matchBase, const uint32_t* __restrict__ firstBad,
+                                                     const uint32_t* __restrict__ firstBad,
                                                      int* __restrict__ status)
 {
   const uint32_t b = blockIdx.x;
@@ -4677,7 +4675,7 @@ __global__ __launch_bounds__(64) void k_lazy_correct(const Block* __restrict__ b
   } else {
     // a shortcut nobody assumed: it runs while the copied length stays above MaxSameLetter; it replaces the
     // assumed intervals it overlaps
-    const uint32_t La = mlen[lo - 1 - matchBase];
+    const uint32_t La = mlen[lo - 1];
     Interval x;
     x.lo = lo;
     x.hi = lo + (La - kSameLetter);
@@ -4704,7 +4702,7 @@ template <bool kRmq>
 __device__ __forceinline__ void dp_spec_body(const Block* __restrict__ blocks,
                                                              const DpSeg* __restrict__ dpSegs, uint32_t ndp,
                                                              const uint32_t* __restrict__ mlen,
-                                                             const uint16_t* __restrict__ mdist, uint64_t matchBase,
+                                                             const uint16_t* __restrict__ mdist,
                                                              uint32_t* __restrict__ costAll, uint32_t* __restrict__ sel,
                                                              uint32_t* __restrict__ reach, uint4* __restrict__ segState,
                                                              const uint32_t* __restrict__ longFlag,
@@ -4718,7 +4716,7 @@ __device__ __forceinline__ void dp_spec_body(const Block* __restrict__ blocks,
   const DpSeg G = dpSegs[segIdx];
   const Block B = blocks[G.block];
   const uint32_t lane = threadIdx.x & 63;
-  const uint64_t base = B.start - matchBase;
+  const uint64_t base = B.start;
   const uint32_t* L = mlen + base;
   const uint16_t* D = mdist + base;
   uint32_t* cost = costAll + base;
@@ -5136,17 +5134,17 @@ __device__ __forceinline__ void dp_spec_body(const Block* __restrict__ blocks,
 // would spill 133 and keeps its registers.
 #define SZ4_DP_SPEC_ARGS                                                                                   \
   const Block *__restrict__ blocks, const DpSeg *__restrict__ dpSegs, uint32_t ndp,                        \
-      const uint32_t *__restrict__ mlen, const uint16_t *__restrict__ mdist, uint64_t matchBase,           \
+      const uint32_t *__restrict__ mlen, const uint16_t *__restrict__ mdist,           \
       uint32_t *__restrict__ costAll, uint32_t *__restrict__ sel, uint32_t *__restrict__ reach,            \
       uint4 *__restrict__ segState, const uint32_t *__restrict__ longFlag, uint32_t *__restrict__ upAll,   \
       uint32_t *__restrict__ downAll
 __global__ __launch_bounds__(64 * kSpecWaves) __attribute__((amdgpu_num_sgpr(80))) void k_dp_spec_lean(SZ4_DP_SPEC_ARGS)
 {
-  dp_spec_body<false>(blocks, dpSegs, ndp, mlen, mdist, matchBase, costAll, sel, reach, segState, longFlag, upAll, downAll);
+  dp_spec_body<false>(blocks, dpSegs, ndp, mlen, mdist, costAll, sel, reach, segState, longFlag, upAll, downAll);
 }
 __global__ __launch_bounds__(64 * kSpecWaves) __attribute__((amdgpu_num_sgpr(80))) void k_dp_spec_rmq(SZ4_DP_SPEC_ARGS)
 {
-  dp_spec_body<true>(blocks, dpSegs, ndp, mlen, mdist, matchBase, costAll, sel, reach, segState, longFlag, upAll, downAll);
+  dp_spec_body<true>(blocks, dpSegs, ndp, mlen, mdist, costAll, sel, reach, segState, longFlag, upAll, downAll);
 }
 #undef SZ4_DP_SPEC_ARGS
 
@@ -5175,7 +5173,7 @@ __global__ __launch_bounds__(64) void k_dp_fix(
 const Block* __restrict__ blocks, const DpSeg* __restrict__ dpSegs,
                                                uint32_t ndp, const uint32_t* __restrict__ mlen,
                                                const uint16_t* __restrict__ mdist,
-                                               uint64_t matchBase, uint32_t* __restrict__ costAll,
+                                               uint32_t* __restrict__ costAll,
                                                uint32_t* __restrict__ sel, const uint32_t* __restrict__ reach,
                                                uint4* __restrict__ segState, const uint32_t* __restrict__ longFlag,
                                                uint32_t* __restrict__ upAll, uint32_t* __restrict__ downAll,
@@ -5219,7 +5217,7 @@ const Block* __restrict__ blocks, const DpSeg* __restrict__ dpSegs,
       return;
     }
   }
-  const uint64_t base = B.start - matchBase;
+  const uint64_t base = B.start;
   const uint32_t* L = mlen + base;
   const uint16_t* D = mdist + base;
   const uint32_t* R = reach + base;
@@ -5678,7 +5676,7 @@ const Block* __restrict__ blocks, const DpSeg* __restrict__ dpSegs,
 // registers (loads run three windows ahead); literal stretches are skipped with one ballot.
 __global__ __launch_bounds__(64 * kWalkWaves) void k_walk(const Block* __restrict__ blocks,
                                                           const uint2* __restrict__ walkSegs, uint32_t nwalk,
-                                                          const uint32_t* __restrict__ chosen, uint64_t matchBase,
+                                                          const uint32_t* __restrict__ chosen,
                                                           uint32_t* __restrict__ slotsAll, uint4* __restrict__ state,
                                                           int* __restrict__ status)
 {
@@ -5689,7 +5687,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_walk(const Block* __restric
   const uint2 ws = walkSegs[idx];
   const Block B = blocks[ws.x];
   const uint32_t n = (uint32_t)(B.end - B.start);
-  const uint32_t* L = chosen + (B.start - matchBase);
+  const uint32_t* L = chosen + B.start;
   uint32_t* slots = slotsAll + (uint64_t)idx * (2 * kWalkCap) + kWalkCap;
   const uint32_t a = ws.y * kWalkSeg;
   const uint32_t aNext = a + kWalkSeg < n ? a + kWalkSeg : n;
@@ -5823,7 +5821,7 @@ struct WalkRepair {
 
 __global__ __launch_bounds__(64 * kWalkWaves) void k_walk_fix_spec(const Block* __restrict__ blocks,
                                                                    const uint2* __restrict__ walkSegs, uint32_t nwalk,
-                                                                   const uint32_t* __restrict__ chosen, uint64_t matchBase,
+                                                                   const uint32_t* __restrict__ chosen,
                                                                    uint32_t* __restrict__ slotsAll,
                                                                    const uint4* __restrict__ state, uint4* __restrict__ rec,
                                                                    int* __restrict__ status)
@@ -5839,7 +5837,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_walk_fix_spec(const Block* 
   const uint32_t n = (uint32_t)(B.end - B.start);
   const uint32_t a = ws.y * kWalkSeg, aNext = a + kWalkSeg < n ? a + kWalkSeg : n;
   uint32_t* slots = slotsAll + (uint64_t)idx * (2 * kWalkCap);
-  const WalkRepair W{chosen + (B.start - matchBase), slots, lane};
+  const WalkRepair W{chosen + B.start, slots, lane};
   uint32_t* fix = fixAll[wave];
   // k_walk's exit of k - 1 (this kernel writes no state)
   const uint4 r = W.run(fix, a, aNext, state[idx], state[idx - 1].z, status);
@@ -5850,7 +5848,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_walk_fix_spec(const Block* 
 }
 
 __global__ __launch_bounds__(64) void k_walk_fix_commit(const Block* __restrict__ blocks, const uint32_t* __restrict__ chosen,
-                                                        uint64_t matchBase, uint32_t* __restrict__ slotsAll,
+                                                        uint32_t* __restrict__ slotsAll,
                                                         uint4* __restrict__ state, const uint4* __restrict__ rec,
                                                         int* __restrict__ status)
 {
@@ -5859,7 +5857,7 @@ __global__ __launch_bounds__(64) void k_walk_fix_commit(const Block* __restrict_
   if (B.walkCount < 2) return;
   const uint32_t lane = threadIdx.x;
   const uint32_t n = (uint32_t)(B.end - B.start);
-  const uint32_t* L = chosen + (B.start - matchBase);
+  const uint32_t* L = chosen + B.start;
   uint32_t T = state[B.walkFirst].z;  // true exit of sub-segment 0 (walked from the block start)
   for (uint32_t k0 = 1; k0 < B.walkCount; k0 += 64) {
     const uint32_t cnt = B.walkCount - k0 < 64u ? B.walkCount - k0 : 64u;
@@ -5963,12 +5961,12 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 
 // info[idx] = (token base, end of the last match before, byte size, byte offset) per sub-segment
 __global__ __launch_bounds__(kAsmThreads) void k_seg_scan(const Block* __restrict__ blocks, const uint32_t* __restrict__ chosen,
-                                                          uint64_t matchBase, const uint32_t* __restrict__ slotsAll,
+                                                          const uint32_t* __restrict__ slotsAll,
                                                           const uint4* __restrict__ state, uint4* __restrict__ info)
 {
   __shared__ uint32_t s_sum[kAsmThreads / 64], s_max[kAsmThreads / 64];
   const Block B = blocks[blockIdx.x];
-  const uint32_t* L = chosen + (B.start - matchBase);
+  const uint32_t* L = chosen + B.start;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   uint32_t carrySum = 0, carryMax = 0;
   for (uint32_t k0 = 0; k0 < B.walkCount; k0 += kAsmThreads) {
@@ -6009,7 +6007,7 @@ __global__ __launch_bounds__(kAsmThreads) void k_seg_scan(const Block* __restric
 // tokens of one sub-segment; blockTail[b] = (matches of the block, bytes of its closing literal run)
 __global__ __launch_bounds__(64 * kSegWaves) void k_seg_tokens(const Block* __restrict__ blocks, const uint2* __restrict__ walkSegs,
                                                               uint32_t nwalk, const uint32_t* __restrict__ chosen,
-                                                              const uint16_t* __restrict__ mdist, uint64_t matchBase,
+                                                              const uint16_t* __restrict__ mdist,
                                                               const uint32_t* __restrict__ slotsAll, const uint4* __restrict__ state,
                                                               uint4* __restrict__ info, Token* __restrict__ tokAll,
                                                               uint2* __restrict__ blockTail)
@@ -6021,8 +6019,8 @@ __global__ __launch_bounds__(64 * kSegWaves) void k_seg_tokens(const Block* __re
   const uint2 ws = walkSegs[idx];
   const Block B = blocks[ws.x];
   const uint32_t n = (uint32_t)(B.end - B.start);
-  const uint32_t* L = chosen + (B.start - matchBase);
-  const uint16_t* D = mdist + (B.start - matchBase);
+  const uint32_t* L = chosen + B.start;
+  const uint16_t* D = mdist + B.start;
   const uint4 st = state[idx];
   const uint4 inf = info[idx];
   const uint32_t m = st.y - st.x;
@@ -6235,9 +6233,9 @@ __global__ __launch_bounds__(64 * kSegWaves) void k_write_seg(const uint8_t* __r
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-void launch_runs(const uint8_t* in, const Block* blocks, uint32_t nblocks, Interval* iv, uint32_t* ivCount, hipStream_t s)
+void launch_runs(const PipeArgs& a, hipStream_t s)
 {
-  if (nblocks) hipLaunchKernelGGL(k_runs, dim3(nblocks), dim3(256), 0, s, in, blocks, iv, ivCount);
+  if (a.nblocks) hipLaunchKernelGGL(k_runs, dim3(a.nblocks), dim3(256), 0, s, a.in, a.blocks, a.iv, a.ivCount);
 }
 
 
@@ -6245,149 +6243,133 @@ uint32_t dp_side_positions() { return kDpSideStride; }
 
 uint32_t find_lds_bytes() { return 65536 + 16; }
 
-void launch_find(int pass, const uint8_t* in, const Segment* segs, uint32_t nsegs, const Block* blocks, const Interval* iv,
-                 const uint32_t* ivCount, uint2* compact, uint2* scratch, uint32_t* rank, uint32_t maxChain,
-                 uint32_t* mlen, uint16_t* mdist, uint64_t matchBase, uint32_t* longBits, uint32_t* segLong,
-                 uint32_t* longFlag, uint32_t* specLen, uint32_t* specDist, uint64_t* segTail, bool ldsWindow,
-                 hipStream_t s)
+// dynamic-LDS limits are per function and device: set them on every launch (a host-side call,
+// no synchronisation) rather than caching them process-wide
+static void find_dyn_lds(const void* fn, uint32_t bytes)
 {
-  static_assert(sizeof(SortLds) <= 65536, "the fused sort's shared memory must fit the window buffer");
-  static_assert(kOutTile * 4u <= 65536u + 16u, "a result tile must fit the window buffer");
-  if (!nsegs) return;
-  const bool unlimited = maxChain >= 65535u;
-  if (ldsWindow) {
-    // dynamic-LDS limits are per function and device: set them on every launch (a host-side call,
-    // no synchronisation) rather than caching them process-wide
-    const void* fn = pass == 1 ? (const void*)k_find_sorted_lds
-                     : unlimited ? (const void*)k_find_long9_lds : (const void*)k_find<true>;
-    hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)find_lds_bytes());
-    if (pass == 1)
-      hipLaunchKernelGGL(k_find_sorted_lds, dim3(nsegs), dim3(kFindThreads), find_lds_bytes(), s, in, segs, blocks, iv,
-                         ivCount, compact, maxChain, mlen, mdist, matchBase, longBits, segLong, scratch, rank);
-    else if (unlimited) {
-      // big key groups first (left-maximal candidates + text-order prefix maximum), then pass 2
-      hipFuncSetAttribute((const void*)k_find_big<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)find_lds_bytes());
-      for (uint32_t resolve = 0; resolve < 2; resolve++)
-        hipLaunchKernelGGL(k_find_big<true>, dim3(nsegs), dim3(kFindThreads), find_lds_bytes(), s, in, segs, blocks, iv, ivCount,
-                           compact, scratch, longBits, segLong, mlen, mdist, matchBase, specLen, segTail, specDist, rank, longFlag, resolve);
-      for (int fix = 0; fix < 2; fix++)
-        hipLaunchKernelGGL(k_find_long9_lds, dim3(nsegs), dim3(kFindThreads), find_lds_bytes(), s, in, segs, blocks, iv,
-                           ivCount, compact, scratch, rank, longBits, segLong, mlen, mdist, matchBase, longFlag, specLen,
-                           specDist, fix);
-    } else
-      hipLaunchKernelGGL(k_find<true>, dim3(nsegs), dim3(kFindThreads), find_lds_bytes(), s, in, segs, blocks, iv, ivCount,
-                         compact, rank, maxChain, mlen, mdist, matchBase, longFlag, segLong);
+  if (bytes) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
+// kLds: the kernels that keep the segment's window in LDS (find_lds_bytes() each); the others read it from HBM
+template <bool kLds>
+static void find_launch(int pass, const PipeArgs& a, hipStream_t s)
+{
+  constexpr auto sorted = kLds ? k_find_sorted_lds : k_find_sorted_hbm;
+  constexpr auto long9 = kLds ? k_find_long9_lds : k_find_long9_hbm;
+  // HBM windows: the sort and the text-order result tiles use the same buffer (at least 64 KiB); pass 2
+  // keeps the segment's own 64 Ki targets and 64 bytes more; k_find<false> uses no dynamic LDS
+  const uint32_t sortedLds = kLds ? find_lds_bytes() : kOutTile * 4u;
+  const uint32_t longLds = kLds ? find_lds_bytes() : 65536u + 256u;
+  const uint32_t chainLds = kLds ? find_lds_bytes() : 0u;
+  const dim3 grid(a.nsegs), block(kFindThreads);
+  uint2 *compact = a.elemB, *scratch = a.elemA;
+  uint32_t *specLen = a.cost, *specDist = a.reach;
+  if (pass == 1) {
+    find_dyn_lds((const void*)sorted, sortedLds);
+    hipLaunchKernelGGL(sorted, grid, block, sortedLds, s, a.in, a.segs, a.blocks, a.iv, a.ivCount, compact, a.maxChain,
+                       a.mlen, a.mdist, a.longBits, a.segLong, scratch, a.rank);
+  } else if (a.maxChain >= 65535u) {
+    // big key groups first (left-maximal candidates + text-order prefix maximum), then pass 2
+    find_dyn_lds((const void*)k_find_big<kLds>, longLds);
+    for (uint32_t resolve = 0; resolve < 2; resolve++)
+      hipLaunchKernelGGL(k_find_big<kLds>, grid, block, longLds, s, a.in, a.segs, a.blocks, a.iv, a.ivCount, compact,
+                         scratch, a.longBits, a.segLong, a.mlen, a.mdist, specLen, a.segTail, specDist, a.rank, a.longFlag,
+                         resolve);
+    find_dyn_lds((const void*)long9, longLds);
+    for (int fix = 0; fix < 2; fix++)
+      hipLaunchKernelGGL(long9, grid, block, longLds, s, a.in, a.segs, a.blocks, a.iv, a.ivCount, compact, scratch, a.rank,
+                         a.longBits, a.segLong, a.mlen, a.mdist, a.longFlag, specLen, specDist, fix);
   } else {
-    if (pass == 1) {
-      // the sort and the text-order result tiles use the same buffer: at least 64 KiB
-      const uint32_t lds = kOutTile * 4u;
-      hipFuncSetAttribute((const void*)k_find_sorted_hbm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(k_find_sorted_hbm, dim3(nsegs), dim3(kFindThreads), lds, s, in, segs, blocks, iv, ivCount,
-                         compact, maxChain, mlen, mdist, matchBase, longBits, segLong, scratch, rank);
-    }
-    else if (unlimited) {
-      // (the segment's own 64 Ki targets and 64 bytes more)
-      const uint32_t bigLds = 65536u + 256u;
-      hipFuncSetAttribute((const void*)k_find_big<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bigLds);
-      for (uint32_t resolve = 0; resolve < 2; resolve++)
-        hipLaunchKernelGGL(k_find_big<false>, dim3(nsegs), dim3(kFindThreads), bigLds, s, in, segs, blocks, iv, ivCount,
-                           compact, scratch, longBits, segLong, mlen, mdist, matchBase, specLen, segTail, specDist, rank, longFlag, resolve);
-      // (the segment's own 64 Ki targets and 64 bytes more)
-      const uint32_t l9Lds = 65536u + 256u;
-      hipFuncSetAttribute((const void*)k_find_long9_hbm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l9Lds);
-      for (int fix = 0; fix < 2; fix++)
-        hipLaunchKernelGGL(k_find_long9_hbm, dim3(nsegs), dim3(kFindThreads), l9Lds, s, in, segs, blocks, iv, ivCount,
-                           compact, scratch, rank, longBits, segLong, mlen, mdist, matchBase, longFlag, specLen, specDist,
-                           fix);
-    }
-    else
-      hipLaunchKernelGGL(k_find<false>, dim3(nsegs), dim3(kFindThreads), 0, s, in, segs, blocks, iv, ivCount, compact, rank,
-                         maxChain, mlen, mdist, matchBase, longFlag, segLong);
+    find_dyn_lds((const void*)k_find<kLds>, chainLds);
+    hipLaunchKernelGGL(k_find<kLds>, grid, block, chainLds, s, a.in, a.segs, a.blocks, a.iv, a.ivCount, compact, a.rank,
+                       a.maxChain, a.mlen, a.mdist, a.longFlag, a.segLong);
   }
 }
 
-void launch_prep(const uint8_t* in, const Block* blocks, uint32_t nblocks, Interval* iv, uint32_t* ivCount, uint32_t maxChain,
-                 uint32_t* mlen, uint16_t* mdist, uint64_t matchBase, uint32_t* sel, const uint32_t* longFlag, int* status,
-                 hipStream_t s)
+void launch_find(int pass, const PipeArgs& a, hipStream_t s)
 {
-  if (nblocks)
-    hipLaunchKernelGGL(k_prep, dim3(nblocks), dim3(64), 0, s, in, blocks, iv, ivCount, maxChain, mlen, mdist, matchBase, sel,
-                       longFlag, status);
+  static_assert(sizeof(SortLds) <= 65536, "the fused sort's shared memory must fit the window buffer");
+  static_assert(kOutTile * 4u <= 65536u + 16u, "a result tile must fit the window buffer");
+  if (!a.nsegs) return;
+  if (a.ldsWindow) find_launch<true>(pass, a, s);
+  else find_launch<false>(pass, a, s);
 }
 
-void launch_lazy(const uint8_t* in, const Block* blocks, uint32_t nblocks, const uint2* walkSegs, uint32_t nwalk,
-                 Interval* iv, uint32_t* ivCount, const uint32_t* longFlag, uint32_t* mlen, const uint16_t* mdist,
-                 uint64_t matchBase, uint32_t* slots, uint4* state, uint32_t* firstBad, int* status, hipStream_t s)
+void launch_prep(const PipeArgs& a, hipStream_t s)
 {
-  if (!nblocks || !nwalk) return;
-  const uint32_t grid = (nwalk + kWalkWaves - 1) / kWalkWaves;
-  hipLaunchKernelGGL(k_lazy_walk, dim3(grid), dim3(64 * kWalkWaves), 0, s, blocks, walkSegs, nwalk, iv, ivCount, mlen,
-                     matchBase, slots, state);
-  hipLaunchKernelGGL(k_lazy_join, dim3(grid), dim3(64 * kWalkWaves), 0, s, blocks, walkSegs, nwalk, iv, ivCount, mlen,
-                     matchBase, slots, state);
-  hipLaunchKernelGGL(k_lazy_fix, dim3(nblocks), dim3(64), 0, s, blocks, iv, ivCount, mlen, matchBase, slots, state, status);
-  hipLaunchKernelGGL(k_lazy_clear, dim3(grid), dim3(64 * kWalkWaves), 0, s, blocks, walkSegs, nwalk, iv, ivCount, mlen,
-                     matchBase, slots, state);
-  hipMemsetAsync(firstBad, 0xFF, (size_t)nblocks * 4, s);
-  hipLaunchKernelGGL(k_lazy_check, dim3(grid), dim3(64 * kWalkWaves), 0, s, in, blocks, walkSegs, nwalk, iv, ivCount, longFlag,
-                     mlen, mdist, matchBase, slots, state, firstBad);
-  hipLaunchKernelGGL(k_lazy_correct, dim3(nblocks), dim3(64), 0, s, blocks, iv, ivCount, mlen, matchBase, firstBad, status);
+  if (a.nblocks)
+    hipLaunchKernelGGL(k_prep, dim3(a.nblocks), dim3(64), 0, s, a.in, a.blocks, a.iv, a.ivCount, a.maxChain, a.mlen, a.mdist,
+                       a.sel, a.longFlag, a.status);
+}
+
+void launch_lazy(const PipeArgs& a, hipStream_t s)
+{
+  if (!a.nblocks || !a.nwalk) return;
+  const dim3 walks((a.nwalk + kWalkWaves - 1) / kWalkWaves), walkBlock(64 * kWalkWaves);
+  uint32_t* firstBad = a.blockBytes;  // free until the token walk
+  hipLaunchKernelGGL(k_lazy_walk, walks, walkBlock, 0, s, a.blocks, a.walkSegs, a.nwalk, a.iv, a.ivCount, a.mlen,
+                     a.lazySlots, a.walkState);
+  hipLaunchKernelGGL(k_lazy_join, walks, walkBlock, 0, s, a.blocks, a.walkSegs, a.nwalk, a.iv, a.ivCount, a.mlen,
+                     a.lazySlots, a.walkState);
+  hipLaunchKernelGGL(k_lazy_fix, dim3(a.nblocks), dim3(64), 0, s, a.blocks, a.iv, a.ivCount, a.mlen, a.lazySlots,
+                     a.walkState, a.status);
+  hipLaunchKernelGGL(k_lazy_clear, walks, walkBlock, 0, s, a.blocks, a.walkSegs, a.nwalk, a.iv, a.ivCount, a.mlen,
+                     a.lazySlots, a.walkState);
+  hipMemsetAsync(firstBad, 0xFF, (size_t)a.nblocks * 4, s);
+  hipLaunchKernelGGL(k_lazy_check, walks, walkBlock, 0, s, a.in, a.blocks, a.walkSegs, a.nwalk, a.iv, a.ivCount, a.longFlag,
+                     a.mlen, a.mdist, a.lazySlots, a.walkState, firstBad);
+  hipLaunchKernelGGL(k_lazy_correct, dim3(a.nblocks), dim3(64), 0, s, a.blocks, a.iv, a.ivCount, a.mlen, firstBad,
+                     a.status);
 }
 
 uint32_t lazy_slots_per_walk() { return 2 * kLazyCap; }
 
-void launch_parse(const uint8_t* in, const Block* blocks, uint32_t nblocks, const DpSeg* dpSegs, uint32_t ndp,
-                  uint32_t maxDpCount, const uint32_t* ivCount, uint32_t maxChain, uint32_t* mlen, const uint16_t* mdist, uint64_t matchBase,
-                  uint32_t* cost, uint32_t* sel, uint32_t* reach, uint4* segState, const uint32_t* longFlag, uint32_t* rmqUp,
-                  uint32_t* rmqDown, uint2* dpSide, uint4* dpRec, int* status, hipStream_t s)
+void launch_parse(const PipeArgs& a, hipStream_t s)
 {
-  (void)in;
-  if (!nblocks) return;
-  if (maxChain <= (uint32_t)kGreedyMax || !ndp) return;
+  if (!a.nblocks) return;
+  if (a.maxChain <= (uint32_t)kGreedyMax || !a.ndp) return;
   // every segment is parsed by exactly one of the two instantiations (by its block's longFlag)
-  hipLaunchKernelGGL(k_dp_spec_lean, dim3((ndp + kSpecWaves - 1) / kSpecWaves), dim3(64 * kSpecWaves), 0, s, blocks, dpSegs,
-                     ndp, mlen, mdist, matchBase, cost, sel, reach, segState, longFlag, rmqUp, rmqDown);
-  hipLaunchKernelGGL(k_dp_spec_rmq, dim3((ndp + kSpecWaves - 1) / kSpecWaves), dim3(64 * kSpecWaves), 0, s, blocks, dpSegs,
-                     ndp, mlen, mdist, matchBase, cost, sel, reach, segState, longFlag, rmqUp, rmqDown);
-  hipLaunchKernelGGL(k_dp_fix<true>, dim3(ndp), dim3(64), 0, s, blocks, dpSegs, ndp, mlen, mdist, matchBase, cost, sel,
-                     reach, segState, longFlag, rmqUp, rmqDown, dpSide, dpRec, 0u);
-  const uint32_t tab = maxDpCount < 1u ? 1u : maxDpCount > kMaxDpSegs ? kMaxDpSegs : maxDpCount;
-  hipLaunchKernelGGL(k_dp_fix<false>, dim3(nblocks), dim3(64), 4 * tab * sizeof(uint32_t), s, blocks, dpSegs, ndp, mlen, mdist,
-                     matchBase, cost, sel, reach, segState, longFlag, rmqUp, rmqDown, dpSide, dpRec, tab);
+  const dim3 specGrid((a.ndp + kSpecWaves - 1) / kSpecWaves), specBlock(64 * kSpecWaves);
+  hipLaunchKernelGGL(k_dp_spec_lean, specGrid, specBlock, 0, s, a.blocks, a.dpSegs, a.ndp, a.mlen, a.mdist, a.cost, a.sel,
+                     a.reach, a.segState, a.longFlag, a.rmqUp, a.rmqDown);
+  hipLaunchKernelGGL(k_dp_spec_rmq, specGrid, specBlock, 0, s, a.blocks, a.dpSegs, a.ndp, a.mlen, a.mdist, a.cost, a.sel,
+                     a.reach, a.segState, a.longFlag, a.rmqUp, a.rmqDown);
+  hipLaunchKernelGGL(k_dp_fix<true>, dim3(a.ndp), dim3(64), 0, s, a.blocks, a.dpSegs, a.ndp, a.mlen, a.mdist, a.cost, a.sel,
+                     a.reach, a.segState, a.longFlag, a.rmqUp, a.rmqDown, a.dpSide, a.dpRec, 0u);
+  const uint32_t tab = a.maxDpCount < 1u ? 1u : a.maxDpCount > kMaxDpSegs ? kMaxDpSegs : a.maxDpCount;
+  hipLaunchKernelGGL(k_dp_fix<false>, dim3(a.nblocks), dim3(64), 4 * tab * sizeof(uint32_t), s, a.blocks, a.dpSegs, a.ndp,
+                     a.mlen, a.mdist, a.cost, a.sel, a.reach, a.segState, a.longFlag, a.rmqUp, a.rmqDown, a.dpSide, a.dpRec,
+                     tab);
 }
 
-void launch_emit(const uint8_t* in, const Block* blocks, uint32_t nblocks, const uint2* walkSegs, uint32_t nwalk,
-                 uint32_t maxChain, const uint32_t* chosen, const uint16_t* mdist, uint64_t matchBase, uint32_t* walkSlots,
-                 uint4* walkState, uint32_t* posList, Token* tokens, uint32_t* ntok, uint32_t* blockBytes,
-                 uint64_t* offsets, uint8_t* out, uint64_t headerLen, int* status, hipStream_t s)
+void launch_emit(const PipeArgs& a, hipStream_t s)
 {
-  if (!nblocks) return;
-  if (maxChain > 0 && nwalk) {
-    hipLaunchKernelGGL(k_walk, dim3((nwalk + kWalkWaves - 1) / kWalkWaves), dim3(64 * kWalkWaves), 0, s, blocks, walkSegs,
-                       nwalk, chosen, matchBase, walkSlots, walkState, status);
+  if (!a.nblocks) return;
+  const bool walk = a.maxChain > 0 && a.nwalk;
+  const dim3 walks((a.nwalk + kWalkWaves - 1) / kWalkWaves), walkBlock(64 * kWalkWaves);
+  const dim3 segGrid((a.nwalk + kSegWaves - 1) / kSegWaves), segBlock(64 * kSegWaves);
+  // per-sub-segment scratch in the parse's reach array (free by now): the repair records, then the
+  // token counts
+  uint4* info = reinterpret_cast<uint4*>(a.reach);
+  uint2* blockTail = reinterpret_cast<uint2*>(info + a.nwalk);
+  if (walk) {
+    hipLaunchKernelGGL(k_walk, walks, walkBlock, 0, s, a.blocks, a.walkSegs, a.nwalk, a.chosen, a.walkSlots, a.walkState,
+                       a.status);
+    hipLaunchKernelGGL(k_walk_fix_spec, walks, walkBlock, 0, s, a.blocks, a.walkSegs, a.nwalk, a.chosen, a.walkSlots,
+                       a.walkState, info, a.status);
+    hipLaunchKernelGGL(k_walk_fix_commit, dim3(a.nblocks), dim3(64), 0, s, a.blocks, a.chosen, a.walkSlots, a.walkState,
+                       info, a.status);
+    hipLaunchKernelGGL(k_seg_scan, dim3(a.nblocks), dim3(kAsmThreads), 0, s, a.blocks, a.chosen, a.walkSlots, a.walkState,
+                       info);
+    hipLaunchKernelGGL(k_seg_tokens, segGrid, segBlock, 0, s, a.blocks, a.walkSegs, a.nwalk, a.chosen, a.mdist, a.walkSlots,
+                       a.walkState, info, a.tokens, blockTail);
   }
-  // per-sub-segment scratch in posList (the parse's reach array, free by now): the repair records,
-  // then the token counts
-  uint4* info = reinterpret_cast<uint4*>(posList);
-  if (maxChain > 0 && nwalk) {
-    hipLaunchKernelGGL(k_walk_fix_spec, dim3((nwalk + kWalkWaves - 1) / kWalkWaves), dim3(64 * kWalkWaves), 0, s, blocks,
-                       walkSegs, nwalk, chosen, matchBase, walkSlots, walkState, info, status);
-    hipLaunchKernelGGL(k_walk_fix_commit, dim3(nblocks), dim3(64), 0, s, blocks, chosen, matchBase, walkSlots, walkState, info,
-                       status);
-  }
-  uint2* blockTail = reinterpret_cast<uint2*>(info + nwalk);
-  const uint32_t segGrid = (nwalk + kSegWaves - 1) / kSegWaves;
-  if (maxChain > 0 && nwalk) {
-    hipLaunchKernelGGL(k_seg_scan, dim3(nblocks), dim3(kAsmThreads), 0, s, blocks, chosen, matchBase, walkSlots, walkState, info);
-    hipLaunchKernelGGL(k_seg_tokens, dim3(segGrid), dim3(64 * kSegWaves), 0, s, blocks, walkSegs, nwalk, chosen, mdist, matchBase,
-                       walkSlots, walkState, info, tokens, blockTail);
-  }
-  hipLaunchKernelGGL(k_block_bytes, dim3(nblocks), dim3(kAsmThreads), 0, s, blocks, maxChain, info, blockTail, ntok, blockBytes,
-                     status);
-  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, blockBytes, nblocks, offsets);
-  if (nwalk)
-    hipLaunchKernelGGL(k_write_seg, dim3(segGrid), dim3(64 * kSegWaves), 0, s, in, blocks, walkSegs, nwalk, walkState, info, tokens,
-                       ntok, blockBytes, offsets, out, headerLen);
+  hipLaunchKernelGGL(k_block_bytes, dim3(a.nblocks), dim3(kAsmThreads), 0, s, a.blocks, a.maxChain, info, blockTail, a.ntok,
+                     a.blockBytes, a.status);
+  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, a.blockBytes, a.nblocks, a.offsets);
+  if (a.nwalk)
+    hipLaunchKernelGGL(k_write_seg, segGrid, segBlock, 0, s, a.in, a.blocks, a.walkSegs, a.nwalk, a.walkState, info, a.tokens,
+                       a.ntok, a.blockBytes, a.offsets, a.out, a.headerLen);
 }
 
 }  // namespace sz4

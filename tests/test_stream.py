@@ -208,6 +208,48 @@ def test_dictionary_rounds_bounded_many_runs(compressor, chain):
     assert 1 <= rounds <= 4, rounds
 
 
+def test_call_kinds_do_not_leak_mode():
+    """A stream's mode (dictionary tables, legacy frame, ghost interval slot) belongs to that call alone:
+    compress_blocks, compress_batch and a plain stream that follow it on the same context compress
+    independent blocks, byte for byte the oracle's.  A context of its own fixes the order of the calls."""
+    import smallz4_amd
+    HDR, END = bytes([0x04, 0x22, 0x4D, 0x18, 0x40, 0x70, 0xDF]), b"\0\0\0\0"
+    text = synth.enwik8_like(300000, seed=101)
+    dictionary = synth.enwik8_like(70000, seed=102)
+    uniform = synth.enwik8_like(200001, seed=103)
+    pool = synth.enwik8_like(1 + 200 + 5000 + 70000 + 66000, seed=104)
+    items, at = [], 0
+    for n in [1, 200, 5000, 70000, 0, 66000]:
+        items.append(pool[at:at + n])
+        at += n
+    want = {}
+    for chain in (65535, 3):
+        want[chain] = (HDR + b"".join(pyoracle.oz_block(uniform[o:o + 65536], chain) for o in range(0, len(uniform), 65536)) + END,
+                       [pyoracle.oz_block(x, chain) for x in items])
+    comp = smallz4_amd.Compressor(device=0)
+
+    def independent_calls(chain, after):
+        assert comp.compress_blocks(uniform, 65536, chain) == want[chain][0], (after, chain)
+        got = comp.compress_batch(items, chain)
+        assert len(got) == len(items)
+        for i, (g, w) in enumerate(zip(got, want[chain][1])):
+            assert g == w, (after, chain, i)
+
+    try:
+        for chain in (65535, 3):
+            assert comp.lz4(text, chain, dictionary) == pyoracle.oz_lz4(text, chain, dictionary), chain
+            independent_calls(chain, "dictionary stream")
+            assert comp.lz4(text, chain) == pyoracle.oz_lz4(text, chain), chain
+        # a zero run across the chunk boundary leaves a ghost interval; the second stream ends in legacy mode
+        comp.set_stream_chunk(M)
+        run = synth.enwik8_like(M - 40000, seed=105) + bytes(110000) + synth.enwik8_like(70000, seed=106)
+        for legacy in (False, True):
+            assert comp.lz4(run, 2, b"", legacy) == pyoracle.oz_lz4(run, 2, b"", legacy), legacy
+            independent_calls(65535, "legacy stream" if legacy else "ghost stream")
+    finally:
+        comp.close()
+
+
 @pytest.mark.parametrize("chain", [3, 65535])
 def test_chunked_legacy(chunked, chain):
     data = synth.enwik8_like(2 * (8 << 20) + 300000, seed=66)
