@@ -1,8 +1,9 @@
 // sz4_host.cpp -- host driver behind the C ABI in include/smallz4_amd.h.
 //
-// Builds the block / segment plan for a job, keeps device scratch resident in
-// HBM (grow-only, so repeated calls allocate nothing), launches the kernel
-// pipeline of sz4_kernels.hip on one HIP stream and assembles the frame.
+// Plans a job (sz4_plan.h: one Plan per context, rebuilt when its key differs),
+// keeps device scratch resident in HBM (sz4_mem.h: grow-only, so repeated calls
+// allocate nothing), launches the kernel pipeline of sz4_kernels.hip on one HIP
+// stream and assembles the frame.
 //
 // Three job shapes:
 //   * independent blocks (sz4_compress_blocks_device): every block compressed
@@ -27,13 +28,14 @@
 
 #include "../../include/smallz4_amd.h"
 #include "sz4_internal.h"
+#include "sz4_mem.h"
+#include "sz4_plan.h"
 
 using namespace sz4;
 
 namespace {
 
 constexpr uint64_t kPad = 64;                 // bytes of slack after every staged input
-constexpr uint64_t kSegTargets = 65536;       // target positions per segment
 // batch API pieces: at most 448 MiB of input, split evenly (a rank's 1.25 GiB slice of configs[4]: three
 // pieces of 427 MiB), so that the scratch (48.6 B per piece byte at 256 KiB blocks) stays under ~21 GiB.
 // Round 5's 1.5 GiB pieces took ~61 GiB for +14 % on configs[4]: the slice in ONE piece runs the per-block
@@ -48,121 +50,10 @@ constexpr uint64_t kBlockMax = kBlockMaxDict;  // MaxBlockSize (smallz4.h:124)
 // most one interval per MaxSameLetter + 1 bytes; a chunk that needs more than that (the old
 // cap was 4 x kMaxIv = 544 rounds) goes to the replay
 uint32_t dict_round_cap(uint64_t maxBlock) { return 2u * (uint32_t)(maxBlock / (kSameLetter + 1)) + 3u; }
-
-uint64_t token_capacity(uint64_t n) { return n / 2 + 4; }
-
-// Device scratch accounting of one context: the bytes it holds, an optional limit, and a call counter.
-// A buffer records the call that last reserved it; buffers of earlier calls (another kind of call: the
-// stream path's staging, dictionary tables, decoder images) are the ones a growing call may release.
-struct DevBuf;
-struct Budget {
-  uint64_t used = 0;   // bytes held by the context's DevBufs
-  uint64_t limit = 0;  // 0: none (sz4_set_device_limit)
-  uint64_t gen = 1;    // the current call
-  std::vector<DevBuf*> bufs;
-  uint64_t shedCount = 0;  // buffers released by shed()
-  void (*onShed)(void*) = nullptr;
-  void* owner = nullptr;
-  uint64_t shed();  // releases every buffer the current call has not reserved; returns the bytes freed
-};
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  Budget* bud = nullptr;
-  uint64_t lastGen = 0;
-  hipError_t reserve(size_t bytes)
-  {
-    if (bud) lastGen = bud->gen;
-    if (bytes <= cap) return hipSuccess;
-    size_t want = bytes + bytes / 32 + 4096;  // slack: a slightly larger next call does not reallocate
-    if (bud && bud->limit) {
-      if (bud->used - cap + want > bud->limit) want = bytes;
-      if (bud->used - cap + want > bud->limit) bud->shed();
-      if (bud->used - cap + want > bud->limit) return hipErrorOutOfMemory;
-    }
-    release();
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipErrorOutOfMemory && bud && bud->shed()) {
-      (void)hipGetLastError();
-      e = hipMalloc(&p, want);
-    }
-    if (e == hipSuccess) {
-      cap = want;
-      if (bud) bud->used += want;
-    } else {
-      p = nullptr;
-      (void)hipGetLastError();  // the failure is returned, not left sticky for the next runtime call
-    }
-    return e;
-  }
-  void release()
-  {
-    if (p) hipFree(p);
-    if (bud) bud->used -= cap;
-    p = nullptr;
-    cap = 0;
-  }
-  // the context could grow this buffer to `bytes` without releasing any other buffer
-  bool fits(size_t bytes) const
-  {
-    return bytes <= cap || !bud || !bud->limit || bud->used - cap + bytes <= bud->limit;
-  }
-  template <class T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
-uint64_t Budget::shed()
-{
-  uint64_t freed = 0;
-  for (DevBuf* b : bufs)
-    if (b->p && b->lastGen != gen) {
-      freed += b->cap;
-      b->release();
-      shedCount++;
-    }
-  if (freed && onShed) onShed(owner);
-  return freed;
-}
-
-// pinned host memory (the stream path's chunk buffers), grow-only
-struct HostBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t bytes)
-  {
-    if (bytes <= cap) return hipSuccess;
-    if (p) hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  void release()
-  {
-    if (p) hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
-// makes the context's device current for the duration of a call and restores the caller's
-struct DeviceGuard {
-  int saved = -1;
-  explicit DeviceGuard(int device)
-  {
-    if (hipGetDevice(&saved) != hipSuccess) saved = -1;
-    if (saved != device) hipSetDevice(device);
-  }
-  ~DeviceGuard()
-  {
-    int now = -1;
-    if (saved >= 0 && hipGetDevice(&now) == hipSuccess && now != saved) hipSetDevice(saved);
-  }
-};
+// smallz4's frame header (smallz4.h:478-496: magic, version 1 with independent-block flag clear, 4 MiB blocks,
+// header checksum) and the legacy frame's magic
+constexpr uint8_t kFrameHeader[7] = {0x04, 0x22, 0x4D, 0x18, 0x40, 0x70, 0xDF};
+constexpr uint8_t kLegacyMagic[4] = {0x02, 0x21, 0x4C, 0x18};
 
 uint32_t xxh32_small(const uint8_t* d, size_t n)
 {
@@ -192,52 +83,49 @@ struct sz4_ctx {
   int stopAfter = 0;
   uint32_t lastChain = 0;
 
-  DevBuf staged, blocks, segs, iv, ivCount, rank, mlen, mdist, cost, ntok, blockBytes, offsets, status;
-  DevBuf dpSegs, reach, segState, walkSegs, walkState, longFlag, longBits, segLong, segTail;
-  DevBuf dpRec;                // the parallel parse-boundary repair's records
-  // One region for the arrays whose lifetimes do not overlap (reserve_all lays it out):
-  //   match search   sort elements A | B  (dead once the search has finished)
-  //   after it       parse choices (sel) | greedy/lazy replay slots, or the parse's range minima UP | DOWN and
-  //                  k_dp_fix's saved speculative values, or the frame tokens | token-walk slots
-  // sel stays live from k_prep (its tail) through the parse to the token walk; the rest are per stage.
-  DevBuf work;
-  uint64_t offElemB = 0, offRmqUp = 0, offRmqDown = 0, offSide = 0, offLazy = 0, offTok = 0, offWalk = 0;
-  uint2* elemA() const { return work.as<uint2>(); }
-  uint2* elemB() const { return reinterpret_cast<uint2*>(work.as<uint8_t>() + offElemB); }
+  // Device scratch.  Every DevBuf is constructed on `budget` and enters its list there: accounting, the device
+  // limit, shed(), sz4_trim and sz4_destroy see a buffer because it is declared, and nowhere else is it named.
+  Budget budget;
+  DevBuf staged{budget}, blocks{budget}, segs{budget}, iv{budget}, ivCount{budget}, rank{budget}, mlen{budget}, mdist{budget};
+  DevBuf cost{budget}, ntok{budget}, blockBytes{budget}, offsets{budget}, status{budget};
+  DevBuf dpSegs{budget}, reach{budget}, segState{budget}, walkSegs{budget}, walkState{budget};
+  DevBuf longFlag{budget}, longBits{budget}, segLong{budget}, segTail{budget};
+  DevBuf dpRec{budget};             // the parallel parse-boundary repair's records
+  DevBuf work{budget};              // the arrays whose lifetimes do not overlap, at plan.off (Plan::work_layout)
+  template <class T>
+  T* work_at(uint64_t off) const { return reinterpret_cast<T*>(work.as<uint8_t>() + off); }
   uint32_t* sel() const { return work.as<uint32_t>(); }
-  uint32_t* rmqUp() const { return reinterpret_cast<uint32_t*>(work.as<uint8_t>() + offRmqUp); }
-  uint32_t* rmqDown() const { return reinterpret_cast<uint32_t*>(work.as<uint8_t>() + offRmqDown); }
-  uint2* dpSide() const { return reinterpret_cast<uint2*>(work.as<uint8_t>() + offSide); }
-  uint32_t* lazySlots() const { return reinterpret_cast<uint32_t*>(work.as<uint8_t>() + offLazy); }
-  Token* tokens() const { return reinterpret_cast<Token*>(work.as<uint8_t>() + offTok); }
-  uint32_t* walkSlots() const { return reinterpret_cast<uint32_t*>(work.as<uint8_t>() + offWalk); }
-  DevBuf dictLast, dictPrevH, dictPrevX;  // dictionary mode: the reference's hash table and both chains
-  DevBuf dictPH, dictPE, dictKeys, dictTemp, dictSc, dictSnap, dictRuns, dictLz;  // dictionary mode on the whole GPU (sz4_dict.hip)
+  DevBuf dictLast{budget}, dictPrevH{budget}, dictPrevX{budget};  // dictionary mode: the reference's hash table and both chains
+  // dictionary mode on the whole GPU (sz4_dict.hip)
+  DevBuf dictPH{budget}, dictPE{budget}, dictKeys{budget}, dictTemp{budget}, dictSc{budget}, dictSnap{budget}, dictRuns{budget};
+  DevBuf dictLz{budget};
   uint32_t dictRounds = 0;  // most rounds a dictionary chunk of the last call took (~0u: one fell back to the in-order replay)
   uint32_t dictMaxRounds = getenv("SZ4_DICT_MAX_ROUNDS") && atoi(getenv("SZ4_DICT_MAX_ROUNDS")) > 0
                                ? (uint32_t)atoi(getenv("SZ4_DICT_MAX_ROUNDS")) : 0u;  // tests: force the replay (0: dict_round_cap)
   bool dictNoGuess = getenv("SZ4_DICT_NO_GUESS") != nullptr;  // A/B: the first round assumes no shortcut interval
   uint64_t dictTempBytes = 0;  // rocPRIM radix sort scratch for dictKeys (queried on first use)
-  DevBuf chunkOut[2];          // stream path: two chunks' blocks (chunk i+1 computes while chunk i downloads)
-  DevBuf stagedS[2];           // stream path: two chunks' staged input (chunk i+1 uploads while chunk i computes)
+  // stream path: two chunks' blocks (chunk i+1 computes while chunk i downloads) and two chunks' staged input
+  // (chunk i+1 uploads while chunk i computes)
+  DevBuf chunkOut[2]{DevBuf{budget}, DevBuf{budget}};
+  DevBuf stagedS[2]{DevBuf{budget}, DevBuf{budget}};
   HostBuf hostIn[2], hostOut[2];
   uint64_t streamChunk = 64ull << 20;  // stream path: input bytes per chunk (rounded to whole blocks)
   uint64_t batchChunk = kBatchChunkDefault;  // sz4_compress_blocks_device: input bytes per internal pipeline run
   bool batchChunkSet = false;          // set explicitly (sz4_set_batch_chunk, SZ4_BATCH_CHUNK): no free-memory cap
   bool batchChunked = false;           // the last sz4_compress_blocks_device call ran in several pieces
-  uint64_t streamPlanKey[5] = {~0ull, 0, 0, 0, 0};  // stream path: the chunk shape the current plan is for
   // stream path, chunk continuation: the previous chunk's last block's final shortcut intervals
   // (ghost slot nblocks of iv/ivCount, B.prev of the first block), uploaded by runs whose RunMode says so
   std::vector<Interval> ghostIv;
   uint32_t ghostN = 0;
-  DevBuf unBlk, unMeta, unFlags, unFrame, unDict, unOut, unSeq;  // decoder (sz4_unlz4*)
-  DevBuf unSubs, unMasks, unImage;  // decoder split mode: sub-segments, their token-start masks, the u32 image
-  DevBuf unIx;                       // decoder: the parallel frame index's candidates and successors
+  // decoder (sz4_unlz4*); split mode: sub-segments, their token-start masks, the u32 image
+  DevBuf unBlk{budget}, unMeta{budget}, unFlags{budget}, unFrame{budget}, unDict{budget}, unOut{budget}, unSeq{budget};
+  DevBuf unSubs{budget}, unMasks{budget}, unImage{budget};
+  DevBuf unIx{budget};                    // decoder: the parallel frame index's candidates and successors
   // ragged batch API: the gather's item table, the block mover's table and the staging area of a piece that
   // runs as two pipeline runs (sz4_compress_batch_device); the batch decoder's extent table
-  DevBuf batchItems, batchMoves, batchTmp, unBatch;
+  DevBuf batchItems{budget}, batchMoves{budget}, batchTmp{budget}, unBatch{budget};
   // typed batch decoder (sz4_unlz4_batch_typed_device): the decoded split items, and k_batch_merge's item table
-  DevBuf unPlanes, mergeItems;
+  DevBuf unPlanes{budget}, mergeItems{budget};
   hipEvent_t evGather[2] = {};  // timing: around k_batch_gather / k_batch_gather_planes
   float gatherMs = 0;
   hipEvent_t evMerge[2] = {};   // timing: around k_batch_merge
@@ -251,19 +139,12 @@ struct sz4_ctx {
   int unSplitMode = getenv("SZ4_UNLZ4_SPLIT") ? atoi(getenv("SZ4_UNLZ4_SPLIT")) : -1;  // -1 auto, 0 never, 1 always
   bool dictSerial = getenv("SZ4_DICT_SERIAL") != nullptr;  // A/B and tests: the in-order replay for every chunk
 
-  std::vector<Block> hBlocks;
-  std::vector<Segment> hSegs;
-  std::vector<DpSeg> hDp;
-  std::vector<uint2> hWalk;
-  uint64_t elemTotal = 0, rankTotal = 0, tokTotal = 0;
-  bool ldsWindow = false;
-  // the plan's device copy (blocks, segments, parse segments, walk sub-segments) is uploaded once per
-  // plan: repeated calls on the same shape skip the uploads
-  uint64_t planVersion = 0, uploadedVersion = ~0ull;
+  // The block plan of the current run: one object for every kind of call, rebuilt when its key differs.
+  // Its device copy (blocks, segments, parse segments, walk sub-segments) is fresh while it holds this
+  // version of the plan at these four addresses: repeated calls on the same shape skip the uploads
+  Plan plan;
+  uint64_t uploadedVersion = ~0ull;
   const void* uploadedAt[4] = {};
-  // plan cache for sz4_compress_blocks_device
-  uint64_t planN = ~0ull;
-  uint32_t planBS = 0;
   std::vector<uint32_t> hostBytes;
 
   hipStream_t stream = nullptr;  // the stream path's compute stream
@@ -273,22 +154,11 @@ struct sz4_ctx {
   std::mutex* poolMu = nullptr;
   std::vector<sz4_ctx*>* poolIdle = nullptr;
 
-  Budget budget;
   // a new call: later reserves record it, and a growing call may release what earlier calls left
   void begin_call()
   {
     err.clear();
     budget.gen++;
-  }
-
-  std::vector<DevBuf*> all_buffers()
-  {
-    return {&staged, &blocks, &segs, &iv, &ivCount, &rank, &mlen, &mdist, &cost, &ntok, &blockBytes, &offsets, &status,
-            &dpSegs, &reach, &segState, &walkSegs, &walkState, &longFlag, &longBits, &segLong, &segTail, &dpRec, &work,
-            &dictLast, &dictPrevH, &dictPrevX, &dictPH, &dictPE, &dictKeys, &dictTemp, &dictSc, &dictSnap, &dictRuns, &dictLz,
-            &chunkOut[0], &chunkOut[1], &stagedS[0], &stagedS[1], &unBlk, &unMeta, &unFlags, &unFrame, &unDict,
-            &unOut, &unSeq, &unSubs, &unMasks, &unImage, &unIx, &batchItems, &batchMoves, &batchTmp, &unBatch,
-            &unPlanes, &mergeItems};
   }
 
   int fail(int code, const char* what, hipError_t e = hipSuccess)
@@ -303,123 +173,15 @@ struct sz4_ctx {
 
 namespace {
 
-// an independent block over the staged bytes [start, end): it sees nothing before its first byte
-Block independent_block(uint64_t start, uint64_t end, uint32_t flags = 0)
-{
-  Block B{};
-  B.start = start;
-  B.end = end;
-  B.low = start;
-  B.cut = kNone;
-  B.prev = kNoBlock;
-  B.flags = flags;
-  return B;
-}
-
-// Targets of block B are positions [start, end - 11) (smallz4.h:629); the window of a segment
-// reaches back 64 KiB - 1 but never below the block's lowest visible byte.
-void add_segments(sz4_ctx* c, uint32_t bi)
-{
-  const Block& B = c->hBlocks[bi];
-  if (B.end - B.start < (uint64_t)kTailNoMatch) return;
-  const uint64_t t1 = B.end - kTailNoMatch + 1;
-  for (uint64_t s0 = B.start; s0 < t1; s0 += kSegTargets) {
-    Segment S{};
-    S.s0 = s0;
-    S.s1 = std::min(s0 + kSegTargets, t1);
-    S.w0 = std::max(B.low, s0 >= kWindow ? s0 - kWindow : 0);
-    S.block = bi;
-    S.elemOff = c->elemTotal;
-    S.rankOff = c->rankTotal;
-    c->elemTotal += S.s1 - S.w0;
-    c->rankTotal += S.s1 - S.s0;
-    c->hSegs.push_back(S);
-  }
-}
-
-void finish_plan(sz4_ctx* c)
-{
-  c->planVersion++;
-  c->tokTotal = 0;
-  for (Block& B : c->hBlocks) {
-    B.tokOff = c->tokTotal;
-    c->tokTotal += token_capacity(B.end - B.start);
-  }
-  c->hSegs.clear();
-  c->elemTotal = c->rankTotal = 0;
-  for (uint32_t b = 0; b < c->hBlocks.size(); b++) add_segments(c, b);
-  // token-walk sub-segments: kWalkSeg positions each
-  c->hWalk.clear();
-  for (uint32_t b = 0; b < c->hBlocks.size(); b++) {
-    Block& B = c->hBlocks[b];
-    const uint64_t n = B.end - B.start;
-    B.walkFirst = (uint32_t)c->hWalk.size();
-    B.walkCount = (uint32_t)((n + kWalkSeg - 1) / kWalkSeg);
-    for (uint32_t k = 0; k < B.walkCount; k++) c->hWalk.push_back(make_uint2(b, k));
-  }
-  // parse segments: positions [0, n - 6] of every block longer than 12 bytes, top segment first
-  c->hDp.clear();
-  for (uint32_t b = 0; b < c->hBlocks.size(); b++) {
-    Block& B = c->hBlocks[b];
-    const uint64_t n = B.end - B.start;
-    B.dpFirst = (uint32_t)c->hDp.size();
-    B.dpCount = 0;
-    if (n <= (uint64_t)kTailNoMatch) continue;
-    const uint64_t top = n - 1 - kTailLiterals;
-    uint64_t seg = dp_segment_size(n);
-    if (n > 65536) {
-      // tuning knob for blocks above 64 KiB: a multiple of 256 (the parse's range-minimum blocks)
-      if (const char* e = getenv("SZ4_DP_SIZE")) {
-        const uint64_t v = strtoull(e, nullptr, 10);
-        if (v >= 1024 && v % 256 == 0 && (n + v - 1) / v <= kMaxDpSegs) seg = v;
-      }
-    }
-    B.dpSize = (uint32_t)seg;
-    for (uint64_t hi = top, k = 0;; hi -= seg, k++) {
-      const uint64_t lo = hi + 1 >= seg ? hi + 1 - seg : 0;
-      c->hDp.push_back(DpSeg{b, (uint32_t)k, (uint32_t)lo, (uint32_t)hi});
-      B.dpCount++;
-      if (lo == 0) break;
-    }
-  }
-  // the finders' LDS-window kernels take the launch when every block's window fits their LDS
-  c->ldsWindow = true;
-  for (const Segment& S : c->hSegs) {
-    const Block& B = c->hBlocks[S.block];
-    if ((B.end - S.w0 + 8 + 3) / 4 * 4 > find_lds_bytes()) c->ldsWindow = false;
-  }
-}
-
-// the shared region's layout for the current plan (sz4_ctx::work); returns its size in bytes
-uint64_t work_layout(sz4_ctx* c, uint64_t stagedBytes)
-{
-  auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
-  const uint64_t nb = c->hBlocks.size();
-  const uint64_t elem = al(c->elemTotal * sizeof(uint2) + 64);
-  c->offElemB = elem;
-  const uint64_t findEnd = 2 * elem;
-  const uint64_t selBytes = al(stagedBytes * 4 + 64), rmq = al((stagedBytes + nb + 8) * 4);
-  c->offRmqUp = selBytes;
-  c->offRmqDown = selBytes + rmq;
-  c->offSide = selBytes + 2 * rmq;
-  const uint64_t parseEnd = c->offSide + al(c->hDp.size() * dp_side_positions() * sizeof(uint2) + 64);
-  c->offLazy = selBytes;
-  const uint64_t lazyEnd = c->offLazy + al(c->hWalk.size() * lazy_slots_per_walk() * 4ull + 64);
-  c->offTok = selBytes;
-  c->offWalk = c->offTok + al(c->tokTotal * sizeof(Token) + 64);
-  const uint64_t emitEnd = c->offWalk + al(c->hWalk.size() * 2 * kWalkCap * 4 + 64);
-  return std::max(std::max(findEnd, parseEnd), std::max(lazyEnd, emitEnd));
-}
-
 int reserve_all(sz4_ctx* c, uint64_t stagedBytes)
 {
-  const uint64_t nb = c->hBlocks.size();
+  const uint64_t nb = c->plan.blocks.size();
   hipError_t e = hipSuccess;
   if ((e = c->blocks.reserve(nb * sizeof(Block) + 64)) ||
-      (e = c->segs.reserve(c->hSegs.size() * sizeof(Segment) + 64)) ||
+      (e = c->segs.reserve(c->plan.segs.size() * sizeof(Segment) + 64)) ||
       (e = c->iv.reserve((nb + 1) * kMaxIv * sizeof(Interval) + 64)) ||
       (e = c->ivCount.reserve((nb + 1) * 4 + 64)) ||
-      (e = c->rank.reserve(c->rankTotal * 4 + 64)) ||
+      (e = c->rank.reserve(c->plan.rankTotal * 4 + 64)) ||
       (e = c->mlen.reserve(stagedBytes * 4 + 64)) ||
       (e = c->mdist.reserve(stagedBytes * 2 + 64)) ||
       (e = c->cost.reserve((stagedBytes + nb + 8) * 4)) ||
@@ -427,17 +189,17 @@ int reserve_all(sz4_ctx* c, uint64_t stagedBytes)
       (e = c->blockBytes.reserve(nb * 4 + 64)) ||
       (e = c->offsets.reserve((nb + 1) * 8 + 64)) ||
       (e = c->status.reserve(64)) ||
-      (e = c->dpSegs.reserve(c->hDp.size() * sizeof(DpSeg) + 64)) ||
+      (e = c->dpSegs.reserve(c->plan.dp.size() * sizeof(DpSeg) + 64)) ||
       (e = c->reach.reserve(stagedBytes * 4 + 64)) ||
-      (e = c->segState.reserve(c->hDp.size() * sizeof(uint4) + 64)) ||
-      (e = c->dpRec.reserve(c->hDp.size() * sizeof(uint4) + 64)) ||
-      (e = c->walkSegs.reserve(c->hWalk.size() * sizeof(uint2) + 64)) ||
-      (e = c->walkState.reserve(c->hWalk.size() * sizeof(uint4) + 64)) ||
+      (e = c->segState.reserve(c->plan.dp.size() * sizeof(uint4) + 64)) ||
+      (e = c->dpRec.reserve(c->plan.dp.size() * sizeof(uint4) + 64)) ||
+      (e = c->walkSegs.reserve(c->plan.walk.size() * sizeof(uint2) + 64)) ||
+      (e = c->walkState.reserve(c->plan.walk.size() * sizeof(uint4) + 64)) ||
       (e = c->longFlag.reserve(nb * 4 + 64)) ||
       (e = c->longBits.reserve(stagedBytes / 8 + 64)) ||
-      (e = c->segLong.reserve(c->hSegs.size() * 4 + 64)) ||
-      (e = c->segTail.reserve(c->hSegs.size() * 8 + 64)) ||
-      (e = c->work.reserve(work_layout(c, stagedBytes))))
+      (e = c->segLong.reserve(c->plan.segs.size() * 4 + 64)) ||
+      (e = c->segTail.reserve(c->plan.segs.size() * 8 + 64)) ||
+      (e = c->work.reserve(c->plan.work_layout(stagedBytes))))
     return c->fail(SZ4_E_NOMEM, "device allocation", e);
   return SZ4_OK;
 }
@@ -445,6 +207,12 @@ int reserve_all(sz4_ctx* c, uint64_t stagedBytes)
 void mark(sz4_ctx* c, int i, hipStream_t s)
 {
   if (c->timing) hipEventRecord(c->ev[i], s);
+}
+
+// sz4_debug_stop_after: the run ends here, once what it has enqueued has finished
+int stop_here(sz4_ctx* c, hipStream_t s)
+{
+  return hipStreamSynchronize(s) == hipSuccess ? SZ4_OK : c->fail(SZ4_E_DEVICE, "pipeline");
 }
 
 int pipeline_finish(sz4_ctx* c, const uint8_t* hdr, uint64_t hdrLen, bool endMark, uint8_t* out, uint64_t outCap,
@@ -466,15 +234,14 @@ PipeArgs pipe_args(const sz4_ctx* c, uint32_t maxChain, const uint8_t* in, uint8
   PipeArgs a{};
   a.in = in;
   a.blocks = c->blocks.as<Block>();
-  a.nblocks = (uint32_t)c->hBlocks.size();
+  a.nblocks = (uint32_t)c->plan.blocks.size();
   a.segs = c->segs.as<Segment>();
-  a.nsegs = (uint32_t)c->hSegs.size();
+  a.nsegs = (uint32_t)c->plan.segs.size();
   a.dpSegs = c->dpSegs.as<DpSeg>();
-  a.ndp = (uint32_t)c->hDp.size();
-  a.maxDpCount = 1;
-  for (const Block& B : c->hBlocks) a.maxDpCount = std::max(a.maxDpCount, B.dpCount);
+  a.ndp = (uint32_t)c->plan.dp.size();
+  a.maxDpCount = c->plan.maxDpCount;
   a.walkSegs = c->walkSegs.as<uint2>();
-  a.nwalk = (uint32_t)c->hWalk.size();
+  a.nwalk = (uint32_t)c->plan.walk.size();
   a.maxChain = maxChain;
   a.iv = c->iv.as<Interval>();
   a.ivCount = c->ivCount.as<uint32_t>();
@@ -488,22 +255,23 @@ PipeArgs pipe_args(const sz4_ctx* c, uint32_t maxChain, const uint8_t* in, uint8
   a.segLong = c->segLong.as<uint32_t>();
   a.segTail = c->segTail.as<uint64_t>();
   a.rank = c->rank.as<uint32_t>();
-  a.elemA = c->elemA();
-  a.elemB = c->elemB();
-  a.rmqUp = c->rmqUp();
-  a.rmqDown = c->rmqDown();
-  a.dpSide = c->dpSide();
+  const Plan::WorkOffsets& off = c->plan.off;
+  a.elemA = c->work.as<uint2>();
+  a.elemB = c->work_at<uint2>(off.elemB);
+  a.rmqUp = c->work_at<uint32_t>(off.rmqUp);
+  a.rmqDown = c->work_at<uint32_t>(off.rmqDown);
+  a.dpSide = c->work_at<uint2>(off.side);
   a.dpRec = c->dpRec.as<uint4>();
   a.segState = c->segState.as<uint4>();
-  a.lazySlots = c->lazySlots();
-  a.walkSlots = c->walkSlots();
+  a.lazySlots = c->work_at<uint32_t>(off.lazy);
+  a.walkSlots = c->work_at<uint32_t>(off.walk);
   a.walkState = c->walkState.as<uint4>();
-  a.tokens = c->tokens();
+  a.tokens = c->work_at<Token>(off.tok);
   a.ntok = c->ntok.as<uint32_t>();
   a.blockBytes = c->blockBytes.as<uint32_t>();
   a.offsets = c->offsets.as<uint64_t>();
   a.status = c->status.as<int>();
-  a.ldsWindow = c->ldsWindow;
+  a.ldsWindow = c->plan.ldsWindow;
   a.out = out;
   a.headerLen = hdrLen;
   // optimal levels tokenize the parse's choices, greedy/lazy levels the (skip-filtered) matches
@@ -516,18 +284,18 @@ PipeArgs pipe_args(const sz4_ctx* c, uint32_t maxChain, const uint8_t* in, uint8
 int run_pipeline(sz4_ctx* c, const RunMode& mode, uint32_t maxChain, const uint8_t* in, const uint8_t* hdr, uint64_t hdrLen,
                  bool endMark, uint8_t* out, uint64_t outCap, uint64_t* outSize, hipStream_t s, bool finish = true)
 {
-  const uint32_t nb = (uint32_t)c->hBlocks.size();
+  const uint32_t nb = (uint32_t)c->plan.blocks.size();
   c->lastChain = maxChain;
   hipError_t e;
   const void* at[4] = {c->blocks.p, c->segs.p, c->dpSegs.p, c->walkSegs.p};
-  const bool fresh = c->uploadedVersion == c->planVersion && memcmp(at, c->uploadedAt, sizeof at) == 0;
+  const bool fresh = c->uploadedVersion == c->plan.version && memcmp(at, c->uploadedAt, sizeof at) == 0;
   if (!fresh &&
-      ((e = hipMemcpyAsync(c->blocks.p, c->hBlocks.data(), nb * sizeof(Block), hipMemcpyHostToDevice, s)) ||
-       (e = hipMemcpyAsync(c->segs.p, c->hSegs.data(), c->hSegs.size() * sizeof(Segment), hipMemcpyHostToDevice, s)) ||
-       (e = hipMemcpyAsync(c->dpSegs.p, c->hDp.data(), c->hDp.size() * sizeof(DpSeg), hipMemcpyHostToDevice, s)) ||
-       (e = hipMemcpyAsync(c->walkSegs.p, c->hWalk.data(), c->hWalk.size() * sizeof(uint2), hipMemcpyHostToDevice, s))))
+      ((e = hipMemcpyAsync(c->blocks.p, c->plan.blocks.data(), nb * sizeof(Block), hipMemcpyHostToDevice, s)) ||
+       (e = hipMemcpyAsync(c->segs.p, c->plan.segs.data(), c->plan.segs.size() * sizeof(Segment), hipMemcpyHostToDevice, s)) ||
+       (e = hipMemcpyAsync(c->dpSegs.p, c->plan.dp.data(), c->plan.dp.size() * sizeof(DpSeg), hipMemcpyHostToDevice, s)) ||
+       (e = hipMemcpyAsync(c->walkSegs.p, c->plan.walk.data(), c->plan.walk.size() * sizeof(uint2), hipMemcpyHostToDevice, s))))
     return c->fail(SZ4_E_DEVICE, "upload plan", e);
-  c->uploadedVersion = c->planVersion;
+  c->uploadedVersion = c->plan.version;
   memcpy(c->uploadedAt, at, sizeof at);
   const PipeArgs P = pipe_args(c, maxChain, in, out, hdrLen);
   if ((e = hipMemsetAsync(P.status, 0, 4, s)) || (e = hipMemsetAsync(P.longFlag, 0, nb * 4, s)))
@@ -552,7 +320,7 @@ int run_pipeline(sz4_ctx* c, const RunMode& mode, uint32_t maxChain, const uint8
         (e = c->dictPrevX.reserve(2 * 65536)))
       return c->fail(SZ4_E_NOMEM, "dictionary tables", e);
     DictArgs A{P};
-    A.hBlocks = c->hBlocks.data();
+    A.hBlocks = c->plan.blocks.data();
     A.dictBack = (uint32_t)mode.dictBack;
     A.cont = mode.cont;
     A.shift = mode.shift;
@@ -564,9 +332,9 @@ int run_pipeline(sz4_ctx* c, const RunMode& mode, uint32_t maxChain, const uint8
     if (c->dictSerial) {
       launch_dict(A, s);  // A/B and tests: the reference's loop replayed in order by one wavefront
     } else {
-      const uint64_t staged = c->hBlocks.back().end + 64;
+      const uint64_t staged = c->plan.blocks.back().end + 64;
       uint64_t maxBlock = 0;
-      for (const Block& B : c->hBlocks) maxBlock = std::max<uint64_t>(maxBlock, B.end - B.start);
+      for (const Block& B : c->plan.blocks) maxBlock = std::max<uint64_t>(maxBlock, B.end - B.start);
       // rocPRIM's scratch size, queried once per context on its own device (0: the query failed)
       if (!c->dictTempBytes && !(c->dictTempBytes = dict_sort_temp_bytes()))
         return c->fail(SZ4_E_DEVICE, "dictionary sort: scratch size query");
@@ -575,7 +343,7 @@ int run_pipeline(sz4_ctx* c, const RunMode& mode, uint32_t maxChain, const uint8
           (e = c->dictKeys.reserve(2 * dict_sort_keys_max() * 8)) || (e = c->dictTemp.reserve(c->dictTempBytes + 64)) ||
           (e = c->dictSc.reserve(dict_sc_bits_bytes(nb, maxBlock))) ||
           (e = c->dictSnap.reserve(lastBytes + 2 * slotBytes)) || (e = c->dictRuns.reserve(dict_run_table_bytes(staged))) ||
-          (e = c->dictLz.reserve(c->hWalk.size() * dict_lz_mask_bytes_per_walk() + 64)))
+          (e = c->dictLz.reserve(c->plan.walk.size() * dict_lz_mask_bytes_per_walk() + 64)))
         return c->fail(SZ4_E_NOMEM, "dictionary scratch", e);
       // the carried tables as this chunk found them: a round that finds other shortcut intervals starts
       // again from here (legacy frames carry nothing: every block starts from empty tables)
@@ -627,7 +395,7 @@ int run_pipeline(sz4_ctx* c, const RunMode& mode, uint32_t maxChain, const uint8
     mark(c, 2, s);
     mark(c, 3, s);
     mark(c, 4, s);
-    if (c->stopAfter == 3) return hipStreamSynchronize(s) == hipSuccess ? SZ4_OK : c->fail(SZ4_E_DEVICE, "pipeline");
+    if (c->stopAfter == 3) return stop_here(c, s);
   }
   // greedy/lazy levels: k_lazy_check verifies the shortcut intervals k_runs assumed; a corrected block
   // needs another sort/find/walk round (each round checks a longer prefix of it)
@@ -635,16 +403,16 @@ int run_pipeline(sz4_ctx* c, const RunMode& mode, uint32_t maxChain, const uint8
     if (maxChain > 0) {
       // k_find_sorted writes every target (shortcut-interval targets "unresolved", for pass 2); its
       // marker bits are OR-ed in
-      if ((e = hipMemsetAsync(P.longBits, 0, c->hBlocks.back().end / 8 + 8, s)))
+      if ((e = hipMemsetAsync(P.longBits, 0, c->plan.blocks.back().end / 8 + 8, s)))
         return c->fail(SZ4_E_DEVICE, "clear matches", e);
     }
     mark(c, 2, s);
     if (maxChain > 0) launch_find(1, P, s);
     mark(c, 3, s);
-    if (c->stopAfter == 2) return hipStreamSynchronize(s) == hipSuccess ? SZ4_OK : c->fail(SZ4_E_DEVICE, "pipeline");
+    if (c->stopAfter == 2) return stop_here(c, s);
     if (maxChain > 0) launch_find(2, P, s);
     mark(c, 4, s);
-    if (c->stopAfter == 3) return hipStreamSynchronize(s) == hipSuccess ? SZ4_OK : c->fail(SZ4_E_DEVICE, "pipeline");
+    if (c->stopAfter == 3) return stop_here(c, s);
     launch_prep(P, s);
     if (maxChain == 0 || maxChain > (uint32_t)kLazyMax) break;
     // greedy/lazy: the reference's skip bookkeeping in parallel over the assumed shortcut intervals, which
@@ -660,7 +428,7 @@ int run_pipeline(sz4_ctx* c, const RunMode& mode, uint32_t maxChain, const uint8
   }
   launch_parse(P, s);
   mark(c, 5, s);
-  if (c->stopAfter == 4) return hipStreamSynchronize(s) == hipSuccess ? SZ4_OK : c->fail(SZ4_E_DEVICE, "pipeline");
+  if (c->stopAfter == 4) return stop_here(c, s);
   launch_emit(P, s);
   mark(c, 6, s);
   if ((e = hipGetLastError())) return c->fail(SZ4_E_DEVICE, "kernel launch", e);
@@ -673,7 +441,7 @@ int run_pipeline(sz4_ctx* c, const RunMode& mode, uint32_t maxChain, const uint8
 int pipeline_finish(sz4_ctx* c, const uint8_t* hdr, uint64_t hdrLen, bool endMark, uint8_t* out, uint64_t outCap,
                     uint64_t* outSize, hipStream_t s)
 {
-  const uint32_t nb = (uint32_t)c->hBlocks.size();
+  const uint32_t nb = (uint32_t)c->plan.blocks.size();
   hipError_t e;
   uint64_t total = 0;
   int status = 0;
@@ -963,30 +731,6 @@ struct StreamChunk {
   uint64_t nextPre() const { return pre + n - shift(); }
 };
 
-// the block plan of a chunk (smallz4.h:572-585: 4 MiB blocks seeing the previous 64 KiB, or 8 MiB
-// independent legacy blocks); cached: equal-shaped chunks reuse the plan and its device copy
-void plan_chunk(sz4_ctx* c, const StreamChunk& ch, int legacy, bool dictMode)
-{
-  const uint64_t key[5] = {ch.pre, ch.n, ch.first ? 1ull : 0ull, (uint64_t)legacy, dictMode ? 1ull : 0ull};
-  if (memcmp(key, c->streamPlanKey, sizeof key) == 0) return;
-  memcpy(c->streamPlanKey, key, sizeof key);
-  const uint64_t bs = legacy ? kBlockMaxLegacy : kBlockMax;
-  c->hBlocks.clear();
-  for (uint64_t st = 0; st < ch.n; st += bs) {
-    Block B = independent_block(ch.pre + st, ch.pre + std::min(st + bs, ch.n), legacy ? kBlkLegacy : 0);
-    if (!legacy && !(st == 0 && ch.first)) {
-      B.low = B.start - kWindow;
-      B.cut = B.start - kTailNoMatch;  // re-inserted by the lookback of the next block
-      B.prev = st == 0 ? kNoBlock - 1 : (uint32_t)c->hBlocks.size() - 1;  // first: the ghost slot, below
-    }
-    c->hBlocks.push_back(B);
-  }
-  const uint32_t nb = (uint32_t)c->hBlocks.size();
-  if (nb && c->hBlocks[0].prev == kNoBlock - 1) c->hBlocks[0].prev = nb;
-  finish_plan(c);
-  c->planN = ~0ull;  // invalidate the independent-block plan cache
-}
-
 // drains the stream path's streams before an early return (nothing may still run on its buffers)
 struct StreamDrain {
   sz4_ctx* c;
@@ -997,6 +741,7 @@ struct StreamDrain {
   }
 };
 
+// header and blocks of the stream; the end mark is stream_compress's
 int stream_compress_body(sz4_ctx* c, sz4_get_bytes get, sz4_send_bytes send, uint32_t maxChain, const uint8_t* dict,
                          uint64_t dictLen, int legacy, void* user, void* out)
 {
@@ -1010,9 +755,8 @@ int stream_compress_body(sz4_ctx* c, sz4_get_bytes get, sz4_send_bytes send, uin
   const uint64_t chunk = std::max<uint64_t>(bs, c->streamChunk / bs * bs);
   const bool dictMode = dictLen != 0;
   // header (smallz4.h:478-496)
-  const uint8_t hm[7] = {0x04, 0x22, 0x4D, 0x18, 0x40, 0x70, 0xDF};
-  const uint8_t hl[4] = {0x02, 0x21, 0x4C, 0x18};
-  send(legacy ? hl : hm, legacy ? 4 : 7, out);
+  if (legacy) send(kLegacyMagic, sizeof kLegacyMagic, out);
+  else send(kFrameHeader, sizeof kFrameHeader, out);
   StreamDrain drain{c};
   bool eof = false, bad = false;
   hipError_t he = hipSuccess;
@@ -1040,7 +784,7 @@ int stream_compress_body(sz4_ctx* c, sz4_get_bytes get, sz4_send_bytes send, uin
     worst.pre = eof ? ch[0].pre : kCarryMax - 1;
     worst.n = span;
     worst.first = eof;
-    plan_chunk(c, worst, legacy, dictMode);
+    c->plan.build_stream(worst.pre, worst.n, worst.first, legacy, dictMode);
     if (int r = reserve_all(c, worst.pre + worst.n + kPad)) return r;
   }
   if (dictMode && ch[0].n) {
@@ -1069,7 +813,7 @@ int stream_compress_body(sz4_ctx* c, sz4_get_bytes get, sz4_send_bytes send, uin
     const uint32_t sl = k & 1;
     const StreamChunk& x = ch[sl];
     mode.ghost = !legacy && !x.first && !dictMode;
-    plan_chunk(c, x, legacy, dictMode);
+    c->plan.build_stream(x.pre, x.n, x.first, legacy, dictMode);
     if (int r = reserve_all(c, x.pre + x.n + kPad)) return r;
     if ((e = hipStreamWaitEvent(c->stream, c->evUp[sl], 0))) return c->fail(SZ4_E_DEVICE, "chunk", e);
     uint64_t unused = 0;
@@ -1087,7 +831,7 @@ int stream_compress_body(sz4_ctx* c, sz4_get_bytes get, sz4_send_bytes send, uin
     if (int r = pipeline_finish(c, nullptr, 0, false, c->chunkOut[sl].as<uint8_t>(), c->chunkOut[sl].cap, size, c->stream))
       return r;
     const uint64_t shift = x.shift();
-    const uint32_t nb = (uint32_t)c->hBlocks.size();
+    const uint32_t nb = (uint32_t)c->plan.blocks.size();
     if (!legacy && !dictMode) {
       uint32_t cnt = 0;
       if ((e = hipMemcpyAsync(&cnt, c->ivCount.as<uint32_t>() + (nb - 1), 4, hipMemcpyDeviceToHost, c->stream)) ||
@@ -1126,13 +870,7 @@ int stream_compress_body(sz4_ctx* c, sz4_get_bytes get, sz4_send_bytes send, uin
     ch[sl].first = false;
     return ch[sl].n != 0 && !he && !bad;
   };
-  if (!ch[0].n) {
-    if (!legacy) {
-      static const uint8_t zero[4] = {0, 0, 0, 0};
-      send(zero, 4, out);  // end mark (smallz4.h:807-812)
-    }
-    return SZ4_OK;
-  }
+  if (!ch[0].n) return SZ4_OK;
   if (int r = upload(0)) return r;
   if (int r = compute(0)) return r;
   bool have = next_chunk(1);
@@ -1182,10 +920,6 @@ int stream_compress_body(sz4_ctx* c, sz4_get_bytes get, sz4_send_bytes send, uin
   if (prof)
     fprintf(stderr, "sz4 stream: finish-wait %.3f s, enqueue %.3f s, download %.3f s, sendBytes %.3f s, getBytes %.3f s, "
             "upload-enqueue %.3f s\n", tp[0], tp[1], tp[2], tp[3], tp[4], tp[5]);
-  if (!legacy) {
-    static const uint8_t zero[4] = {0, 0, 0, 0};
-    send(zero, 4, out);  // end mark (smallz4.h:807-812)
-  }
   return SZ4_OK;
 }
 
@@ -1196,7 +930,11 @@ int stream_compress(sz4_ctx* c, sz4_get_bytes get, sz4_send_bytes send, uint32_t
 {
   c->dictRounds = 0;  // sz4_dict_rounds reports this call's chunks
   try {
-    return stream_compress_body(c, get, send, maxChain, dict, dictLen, legacy, user, sinkUser ? sinkUser : user);
+    void* out = sinkUser ? sinkUser : user;
+    const int r = stream_compress_body(c, get, send, maxChain, dict, dictLen, legacy, user, out);
+    static const uint8_t zero[4] = {0, 0, 0, 0};
+    if (r == SZ4_OK && !legacy) send(zero, 4, out);  // end mark (smallz4.h:807-812)
+    return r;
   } catch (const std::bad_alloc&) {
     return c->fail(SZ4_E_NOMEM, "host allocation");
   }
@@ -1248,7 +986,7 @@ int stream_decompress(sz4_ctx* c, sz4_get_byte get, sz4_send_out send, const uin
   std::vector<uint8_t> hist;  // the last <= 64 KiB before the next chunk's output
   if (dictLen) hist.assign(dict + (dictLen - std::min<uint64_t>(dictLen, 65536)), dict + dictLen);
   std::vector<uint8_t> frame, out, pend;  // pend: output not yet flushed (< 64 KiB)
-  const uint8_t hdr[7] = {0x04, 0x22, 0x4D, 0x18, 0x40, 0x70, 0xDF};
+  const uint8_t* hdr = kFrameHeader;
   const uint64_t budget = std::max<uint64_t>(c->streamChunk / 2, 1u << 20);
   auto decode = [&]() -> int {
     if (frame.size() <= 7) return SZ4_OK;
@@ -1362,8 +1100,6 @@ uint64_t batch_block_cap(uint64_t piece)
   return std::min<uint64_t>(kBatchMaxBlocks, std::max<uint64_t>(64, piece * kScratchPerByte / 4 / kPerBlockScratch));
 }
 
-uint64_t batch_stride(uint64_t size) { return (size + kBatchAlign - 1) / kBatchAlign * kBatchAlign; }
-
 // an item whose window fits the finders' LDS (finish_plan's test: the first segment's window is the whole
 // item, and no later segment's reaches further)
 bool batch_fits_lds(uint64_t size) { return (size + 8 + 3) / 4 * 4 <= find_lds_bytes(); }
@@ -1381,21 +1117,14 @@ int batch_run(sz4_ctx* c, const std::vector<uint64_t>& idx, const void* const* p
   for (uint32_t k = 0; elems && k < nb; k++) planes |= elems[idx[k]] > 1;
   std::vector<BatchItem> items(planes ? 0 : nb);
   std::vector<BatchTyped> typed(planes ? nb : 0);
-  c->hBlocks.clear();
-  uint64_t at = 0;
+  std::vector<uint64_t> runSizes(nb);
+  for (uint32_t k = 0; k < nb; k++) runSizes[k] = sizes[idx[k]];
+  const uint64_t stagedBytes = c->plan.build_ragged(runSizes) + kPad;
   for (uint32_t k = 0; k < nb; k++) {
-    const uint64_t n = sizes[idx[k]];
+    const uint64_t at = c->plan.blocks[k].start, n = runSizes[k];
     if (planes) typed[k] = BatchTyped{(uint64_t)(uintptr_t)ptrs[idx[k]], at, (uint32_t)n, elems[idx[k]]};
     else items[k] = BatchItem{(uint64_t)(uintptr_t)ptrs[idx[k]], at, n};
-    c->hBlocks.push_back(independent_block(at, at + n));
-    at += batch_stride(n);
   }
-  finish_plan(c);
-  // the uniform plan caches describe another plan now: a following call of either kind plans again
-  c->planN = ~0ull;
-  c->planBS = 0;
-  c->streamPlanKey[0] = ~0ull;
-  const uint64_t stagedBytes = at + kPad;
   hipError_t e = hipSuccess;
   if (int r = reserve_all(c, stagedBytes)) return r;
   static_assert(sizeof(BatchTyped) == sizeof(BatchItem), "one table size for both gathers");
@@ -1512,8 +1241,6 @@ int sz4_create(sz4_ctx** ctx, int device, uint64_t reserve_bytes)
   for (auto& e : c->ev) hipEventCreate(&e);
   for (auto& e : c->evGather) hipEventCreate(&e);
   for (auto& e : c->evMerge) hipEventCreate(&e);
-  c->budget.bufs = c->all_buffers();
-  for (DevBuf* b : c->budget.bufs) b->bud = &c->budget;
   c->budget.owner = c;
   // a released plan buffer may come back at the same address: upload the plan again
   c->budget.onShed = [](void* o) { static_cast<sz4_ctx*>(o)->uploadedVersion = ~0ull; };
@@ -1529,7 +1256,7 @@ void sz4_destroy(sz4_ctx* c)
 {
   if (!c) return;
   DeviceGuard guard(c->device);
-  for (DevBuf* b : c->all_buffers()) b->release();
+  for (DevBuf* b : c->budget.bufs) b->release();
   for (HostBuf* b : {&c->hostIn[0], &c->hostIn[1], &c->hostOut[0], &c->hostOut[1]}) b->release();
   for (hipStream_t x : {c->stream, c->upStream, c->downStream})
     if (x) hipStreamDestroy(x);
@@ -1588,7 +1315,7 @@ void sz4_trim(sz4_ctx* c)
   DeviceGuard guard(c->device);
   for (hipStream_t x : {c->stream, c->upStream, c->downStream})
     if (x) hipStreamSynchronize(x);
-  for (DevBuf* b : c->all_buffers()) b->release();
+  for (DevBuf* b : c->budget.bufs) b->release();
   for (HostBuf* b : {&c->hostIn[0], &c->hostIn[1], &c->hostOut[0], &c->hostOut[1]}) b->release();
   c->uploadedVersion = ~0ull;
 }
@@ -1630,8 +1357,7 @@ int sz4_compress_blocks_device(sz4_ctx* c, const void* d_in, uint64_t n, uint32_
   uint64_t hl = 0;
   bool endMark = true;
   if (header == SZ4_HEADER_SMALLZ4) {
-    const uint8_t h[7] = {0x04, 0x22, 0x4D, 0x18, 0x40, 0x70, 0xDF};
-    memcpy(hdr, h, 7);
+    memcpy(hdr, kFrameHeader, 7);
     hl = 7;
   } else if (header == SZ4_HEADER_INDEPENDENT) {
     uint8_t bd = 4;
@@ -1671,22 +1397,13 @@ int sz4_compress_blocks_device(sz4_ctx* c, const void* d_in, uint64_t n, uint32_
   for (uint64_t off = 0; off < n; off += piece) {
     const uint64_t len = std::min(piece, n - off);
     const bool firstPiece = off == 0, lastPiece = off + len == n;
-    if (c->planN != len || c->planBS != block_size) {
-      c->hBlocks.clear();
-      for (uint64_t st = 0; st < len; st += block_size)
-        c->hBlocks.push_back(independent_block(st, std::min<uint64_t>(st + block_size, len)));
-      finish_plan(c);
-      c->planN = len;
-      c->planBS = block_size;
-      c->streamPlanKey[0] = ~0ull;  // invalidate the stream path's plan cache
-    }
+    c->plan.build_uniform(len, block_size);
     hipError_t e = hipSuccess;
     int rr = reserve_all(c, len + kPad);
     if (rr == SZ4_OK && (e = c->staged.reserve(len + kPad))) rr = c->fail(SZ4_E_NOMEM, "staging", e);
     if (rr == SZ4_E_NOMEM && piece > block_size && piece > kPieceFloor) {
       // smaller pieces: the next iteration re-plans this offset with half the piece
       piece = std::max<uint64_t>(block_size, std::max<uint64_t>(kPieceFloor, piece / 2) / block_size * block_size);
-      c->planN = ~0ull;
       off -= piece;  // the loop adds it back
       continue;
     }
@@ -1703,7 +1420,7 @@ int sz4_compress_blocks_device(sz4_ctx* c, const void* d_in, uint64_t n, uint32_
     for (int i = 0; i < kStages; i++) stageSum[i] += c->stageMs[i];
     if (!(firstPiece && lastPiece)) {
       // every piece's block sizes, for sz4_last_block_sizes
-      const uint32_t nb = (uint32_t)c->hBlocks.size();
+      const uint32_t nb = (uint32_t)c->plan.blocks.size();
       const size_t at = c->hostBytes.size();
       c->hostBytes.resize(at + nb);
       if ((e = hipMemcpy(c->hostBytes.data() + at, c->blockBytes.p, nb * 4, hipMemcpyDeviceToHost)))

@@ -1,4 +1,4 @@
-// sz4_internal.h -- descriptors shared by the host driver (sz4_host.cpp) and the
+// sz4_internal.h -- descriptors shared by the host driver (sz4_host.cpp), its planner (sz4_plan.cpp) and the
 // gfx950 kernels (sz4_kernels.hip, sz4_dict.hip), and the launchers between them: the
 // compressor's take one PipeArgs (DictArgs in dictionary mode).  Not part of the public ABI.
 #pragma once
@@ -92,8 +92,21 @@ struct Token {
 };
 constexpr uint32_t kTokLast = 0x80000000u;
 
-// kernels (sz4_kernels.hip)
-uint32_t find_lds_bytes();
+// Sizes the planner (sz4_plan.cpp) shares with the kernels of sz4_kernels.hip that they are built for.
+// The finders' LDS-window kernels hold a 64 KiB block and 16 bytes more:
+constexpr uint32_t kFindLds = 65536 + 16;
+constexpr uint32_t find_lds_bytes() { return kFindLds; }
+// k_dp_fix<true> saves the speculative values it overwrites: kDpSide positions at most (or it gives up), and
+// after them the range-minimum UP/DOWN keys down to the bottom of its convergence point's rmq block
+// (kDpSide + 255 positions at most)
+constexpr uint32_t kDpSide = 512;
+constexpr uint32_t kDpSideKeys = kDpSide + 256;
+constexpr uint32_t kDpSideStride = kDpSide + kDpSideKeys;
+constexpr uint32_t dp_side_positions() { return kDpSideStride; }
+// greedy/lazy replay: searched positions per walk sub-segment (<= 2 per 6 linked + 2), speculative and repaired
+constexpr uint32_t kLazyCap = 1400;
+constexpr uint32_t lazy_slots_per_walk() { return 2 * kLazyCap; }
+
 // The buffers of one pipeline run, as every compressor launcher takes them: the host driver fills one
 // PipeArgs per run (pipe_args in sz4_host.cpp) once all of the run's buffers are reserved.  Arrays "per
 // position" are indexed by the absolute staged position, like Block's fields.
@@ -192,9 +205,7 @@ void launch_prep(const PipeArgs& a, hipStream_t s);
 // k_lazy_clear) over the assumed same-letter shortcut intervals, then their check (k_lazy_check /
 // k_lazy_correct: status kStPrepRound = an interval list was corrected, run sort/find/walk again)
 void launch_lazy(const PipeArgs& a, hipStream_t s);
-uint32_t lazy_slots_per_walk();
 void launch_parse(const PipeArgs& a, hipStream_t s);
-uint32_t dp_side_positions();
 // the token walk over a.chosen, the tokens, the block sizes and the frame body at a.out + a.headerLen
 void launch_emit(const PipeArgs& a, hipStream_t s);
 

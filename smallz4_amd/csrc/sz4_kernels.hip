@@ -4133,7 +4133,7 @@ __global__ __launch_bounds__(64) void k_prep(const uint8_t* __restrict__ in, con
 // searches imply.
 // ================================================================================================
 constexpr int kWalkWaves = 4;         // sub-segments per k_walk / k_lazy_* workgroup
-constexpr uint32_t kLazyCap = 1400;   // searched positions per sub-segment: <= 2 per 6 linked + 2
+// kLazyCap (sz4_internal.h): searched positions per sub-segment, <= 2 per 6 linked + 2
 constexpr uint32_t kLazyEnd = 0x7FFFFFFFu;
 
 // the searched-position chain over a register window of lengths: four 64-position windows in
@@ -5158,11 +5158,8 @@ __global__ __launch_bounds__(64 * kSpecWaves) __attribute__((amdgpu_num_sgpr(80)
 // k_dp_fix<false> (one wavefront per block) then walks the boundaries: a segment whose record is exact
 // only enters the offset tables; the others get their speculative values back and are repaired
 // serially as before.
-constexpr uint32_t kDpSide = 512;
-// range-minimum blocks: k_dp_fix<true> also saves the UP/DOWN keys it overwrites, down to the bottom
-// of its convergence point's rmq block (kDpSide + 255 positions at most), after the cost side
-constexpr uint32_t kDpSideKeys = kDpSide + 256;
-constexpr uint32_t kDpSideStride = kDpSide + kDpSideKeys;
+// kDpSide, kDpSideKeys, kDpSideStride: sz4_internal.h (range-minimum blocks: the UP/DOWN keys k_dp_fix<true>
+// overwrites are saved after the cost side)
 // ... but only in blocks of more than this many parse segments: in a short block the serial walk is
 // short too, while a range-minimum block's parallel repair reads long match ranges at every position it
 // takes (zeros/urandom, 256 KiB blocks: parse 36.3 ms per 268 MB with it, 10.9 ms without)
@@ -6239,10 +6236,6 @@ void launch_runs(const PipeArgs& a, hipStream_t s)
 }
 
 
-uint32_t dp_side_positions() { return kDpSideStride; }
-
-uint32_t find_lds_bytes() { return 65536 + 16; }
-
 // dynamic-LDS limits are per function and device: set them on every launch (a host-side call,
 // no synchronisation) rather than caching them process-wide
 static void find_dyn_lds(const void* fn, uint32_t bytes)
@@ -6321,8 +6314,6 @@ void launch_lazy(const PipeArgs& a, hipStream_t s)
   hipLaunchKernelGGL(k_lazy_correct, dim3(a.nblocks), dim3(64), 0, s, a.blocks, a.iv, a.ivCount, a.mlen, firstBad,
                      a.status);
 }
-
-uint32_t lazy_slots_per_walk() { return 2 * kLazyCap; }
 
 void launch_parse(const PipeArgs& a, hipStream_t s)
 {

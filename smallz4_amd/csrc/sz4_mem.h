@@ -1,0 +1,129 @@
+// sz4_mem.h -- the host driver's memory holders: device scratch with its accounting (Budget, DevBuf),
+// pinned host buffers (HostBuf) and the device guard of a call.  Used by sz4_host.cpp only.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+namespace sz4 {
+
+// Device scratch accounting of one context: the bytes it holds, an optional limit, and a call counter.
+// A buffer records the call that last reserved it; buffers of earlier calls (another kind of call: the
+// stream path's staging, dictionary tables, decoder images) are the ones a growing call may release.
+struct DevBuf;
+struct Budget {
+  uint64_t used = 0;   // bytes held by the context's DevBufs
+  uint64_t limit = 0;  // 0: none (sz4_set_device_limit)
+  uint64_t gen = 1;    // the current call
+  std::vector<DevBuf*> bufs;  // every DevBuf constructed on this budget, in construction order
+  uint64_t shedCount = 0;  // buffers released by shed()
+  void (*onShed)(void*) = nullptr;
+  void* owner = nullptr;
+  inline uint64_t shed();  // releases every buffer the current call has not reserved; returns the bytes freed
+};
+
+// A grow-only device buffer.  It belongs to the budget it is constructed on and enters that budget's list
+// itself, so accounting, shedding, trim and destroy see every buffer that exists; it stays where it was
+// constructed (the list holds its address) and must not outlive the budget's owner.
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  Budget& bud;
+  uint64_t lastGen = 0;
+  explicit DevBuf(Budget& b) : bud(b) { b.bufs.push_back(this); }
+  DevBuf(const DevBuf&) = delete;  // neither copied nor moved
+  DevBuf& operator=(const DevBuf&) = delete;
+  hipError_t reserve(size_t bytes)
+  {
+    lastGen = bud.gen;
+    if (bytes <= cap) return hipSuccess;
+    size_t want = bytes + bytes / 32 + 4096;  // slack: a slightly larger next call does not reallocate
+    if (bud.limit) {
+      if (bud.used - cap + want > bud.limit) want = bytes;
+      if (bud.used - cap + want > bud.limit) bud.shed();
+      if (bud.used - cap + want > bud.limit) return hipErrorOutOfMemory;
+    }
+    release();
+    hipError_t e = hipMalloc(&p, want);
+    if (e == hipErrorOutOfMemory && bud.shed()) {
+      (void)hipGetLastError();
+      e = hipMalloc(&p, want);
+    }
+    if (e == hipSuccess) {
+      cap = want;
+      bud.used += want;
+    } else {
+      p = nullptr;
+      (void)hipGetLastError();  // the failure is returned, not left sticky for the next runtime call
+    }
+    return e;
+  }
+  void release()
+  {
+    if (p) hipFree(p);
+    bud.used -= cap;
+    p = nullptr;
+    cap = 0;
+  }
+  // the context could grow this buffer to `bytes` without releasing any other buffer
+  bool fits(size_t bytes) const { return bytes <= cap || !bud.limit || bud.used - cap + bytes <= bud.limit; }
+  template <class T>
+  T* as() const { return static_cast<T*>(p); }
+};
+
+inline uint64_t Budget::shed()
+{
+  uint64_t freed = 0;
+  for (DevBuf* b : bufs)
+    if (b->p && b->lastGen != gen) {
+      freed += b->cap;
+      b->release();
+      shedCount++;
+    }
+  if (freed && onShed) onShed(owner);
+  return freed;
+}
+
+// pinned host memory (the stream path's chunk buffers), grow-only
+struct HostBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  hipError_t reserve(size_t bytes)
+  {
+    if (bytes <= cap) return hipSuccess;
+    if (p) hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+  }
+  void release()
+  {
+    if (p) hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  template <class T>
+  T* as() const { return static_cast<T*>(p); }
+};
+
+// makes the context's device current for the duration of a call and restores the caller's
+struct DeviceGuard {
+  int saved = -1;
+  explicit DeviceGuard(int device)
+  {
+    if (hipGetDevice(&saved) != hipSuccess) saved = -1;
+    if (saved != device) hipSetDevice(device);
+  }
+  ~DeviceGuard()
+  {
+    int now = -1;
+    if (saved >= 0 && hipGetDevice(&now) == hipSuccess && now != saved) hipSetDevice(saved);
+  }
+};
+
+}  // namespace sz4

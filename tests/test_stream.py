@@ -250,6 +250,52 @@ def test_call_kinds_do_not_leak_mode():
         comp.close()
 
 
+def test_plan_cache_across_call_kinds():
+    """One context keeps one block plan, rebuilt whenever its key (kind of call and shape) differs.  Uniform
+    calls of two block sizes, ragged batches, modern and legacy streams and a trim alternate on one fresh
+    context over the same L = 3 x 65536 + 17 bytes -- a uniform plan of L bytes and a stream chunk of L bytes
+    included -- and every result is the oracle's, byte for byte: no call runs the plan another one left."""
+    import smallz4_amd
+    HDR, END = bytes([0x04, 0x22, 0x4D, 0x18, 0x40, 0x70, 0xDF]), b"\0\0\0\0"
+    L = 3 * 65536 + 17
+    data = synth.enwik8_like(L, seed=107)
+    items, at = [], 0
+    for n in [1, 200, 5000, 70000, 66000]:
+        items.append(data[at:at + n])
+        at += n
+    comp = smallz4_amd.Compressor(device=0)
+
+    def blocks(bs, chain, want, step):
+        assert comp.compress_blocks(data, bs, chain) == want[bs], (step, chain)
+
+    def batch(chain, want, step):
+        got = comp.compress_batch(items, chain)
+        assert len(got) == len(items)
+        for i, (g, w) in enumerate(zip(got, want["items"])):
+            assert g == w, (step, chain, i)
+
+    try:
+        for chain in (65535, 3):
+            want = {bs: HDR + b"".join(pyoracle.oz_block(data[o:o + bs], chain) for o in range(0, L, bs)) + END
+                    for bs in (65536, 32768)}
+            want["items"] = [pyoracle.oz_block(x, chain) for x in items]
+            blocks(65536, chain, want, 1)
+            blocks(32768, chain, want, 2)
+            batch(chain, want, 3)
+            blocks(65536, chain, want, 4)
+            assert comp.lz4(data, chain) == pyoracle.oz_lz4(data, chain), (5, chain)
+            blocks(65536, chain, want, 6)
+            comp.trim()
+            assert comp.device_bytes() == 0, (7, chain)
+            blocks(65536, chain, want, 8)
+            assert comp.lz4(data, chain, b"", True) == pyoracle.oz_lz4(data, chain, b"", True), (9, chain)
+            batch(chain, want, 10)
+        comp.trim()
+        assert comp.device_bytes() == 0
+    finally:
+        comp.close()
+
+
 @pytest.mark.parametrize("chain", [3, 65535])
 def test_chunked_legacy(chunked, chain):
     data = synth.enwik8_like(2 * (8 << 20) + 300000, seed=66)

@@ -215,8 +215,9 @@ def test_unlz4_c_dropin_program(compressor, tmp_path):
 def split():
     """A context whose decoder runs every frame in split mode (SZ4_UNLZ4_SPLIT=1): blocks cut into
     8 KiB sub-segments parsed speculatively and joined to the true token chain (k_unlz4_spec /
-    k_unlz4_fix), decoded one wavefront per sub-segment into a value-or-reference image whose references
-    are resolved by pointer jumping (k_unlz4_sub / k_unlz4_resolve / k_unlz4_pack)."""
+    k_unlz4_fix), decoded one wavefront per sub-segment into a value-or-reference image (k_unlz4_sub);
+    k_unlz4_pack follows every reference to its byte while it packs the output, and
+    unlz4_resolve_passes() reports the longest reference chain (hops) it followed."""
     import smallz4_amd
     os.environ["SZ4_UNLZ4_SPLIT"] = "1"
     try:
