@@ -152,20 +152,6 @@ __device__ __forceinline__ uint32_t wrlane(uint32_t v, uint32_t x, uint32_t l)
   return (uint32_t)sz4_llvm_writelane((int)x, (int)l, (int)v);
 }
 
-template <int kCtrl>
-__device__ __forceinline__ uint32_t dpp(uint32_t v)
-{
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kCtrl, 0xF, 0xF, false);
-}
-constexpr int kQuadSwap1 = 0xB1;      // quad_perm [1,0,3,2]
-constexpr int kQuadSwap2 = 0x4E;      // quad_perm [2,3,0,1]
-constexpr int kRowHalfMirror = 0x141;
-constexpr int kRowMirror = 0x140;
-constexpr int kRowShr = 0x110;        // + n
-constexpr int kWaveShr1 = 0x138;      // wave_shr:1 (whole 64-lane wavefront)
-constexpr int kRowBcast15 = 0x142;    // lane 15 of each row to the next row
-constexpr int kRowBcast31 = 0x143;    // lane 31 to rows 2 and 3
-
 // DPP into the rows of kRowMask only; the other rows (and lanes without a source) keep `old`
 template <int kCtrl, int kRowMask>
 __device__ __forceinline__ uint32_t dpp_rows(uint32_t old, uint32_t v)
@@ -173,24 +159,6 @@ __device__ __forceinline__ uint32_t dpp_rows(uint32_t old, uint32_t v)
   return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, kCtrl, kRowMask, 0xF, false);
 }
 
-
-// every lane receives the min / max of its 16-lane row
-__device__ __forceinline__ uint32_t row_min(uint32_t v)
-{
-  v = min(v, dpp<kQuadSwap1>(v));
-  v = min(v, dpp<kQuadSwap2>(v));
-  v = min(v, dpp<kRowHalfMirror>(v));
-  v = min(v, dpp<kRowMirror>(v));
-  return v;
-}
-__device__ __forceinline__ uint32_t row_max(uint32_t v)
-{
-  v = max(v, dpp<kQuadSwap1>(v));
-  v = max(v, dpp<kQuadSwap2>(v));
-  v = max(v, dpp<kRowHalfMirror>(v));
-  v = max(v, dpp<kRowMirror>(v));
-  return v;
-}
 // inclusive max-scan inside each 16-lane row (lanes below the row start contribute 0)
 __device__ __forceinline__ uint32_t row_scan_max(uint32_t v)
 {
@@ -199,15 +167,6 @@ __device__ __forceinline__ uint32_t row_scan_max(uint32_t v)
   v = max(v, dpp<kRowShr + 4>(v));
   v = max(v, dpp<kRowShr + 8>(v));
   return v;
-}
-// wave-wide min delivered to EVERY lane (no SGPR round trip): rows, then row pairs, then halves
-__device__ __forceinline__ uint32_t wave_min_all(uint32_t v)
-{
-  v = row_min(v);
-  auto a = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-  v = min(a[0], a[1]);
-  auto b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-  return min(b[0], b[1]);
 }
 
 // four wave-wide minima, interleaved so that no DPP step waits on the one before (no s_nop), rows
@@ -248,31 +207,6 @@ __device__ __forceinline__ uint32_t wave_min_fast(uint32_t v)
   v = row_min(v);
   const uint32_t a = rdlane(v, 0), b = rdlane(v, 16), c = rdlane(v, 32), d = rdlane(v, 48);
   return min(min(a, b), min(c, d));
-}
-
-// inclusive wavefront scans by DPP: row shifts 1, 2, 4, 8, then lane 15 of each row into the next row and
-// lane 31 into rows 2-3, lanes without a source taking the identity (0 for + and unsigned max) -- six
-// dependent VALU steps instead of six ds_bpermute round trips
-__device__ __forceinline__ uint32_t wave_incl_scan_add(uint32_t v)
-{
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowShr + 1, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowShr + 2, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowShr + 4, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowShr + 8, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowBcast15, 0xA, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowBcast31, 0xC, 0xF, false);
-  return v;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan_max(uint32_t v)
-{
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowShr + 1, 0xF, 0xF, false));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowShr + 2, 0xF, 0xF, false));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowShr + 4, 0xF, 0xF, false));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowShr + 8, 0xF, 0xF, false));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowBcast15, 0xA, 0xF, false));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowBcast31, 0xC, 0xF, false));
-  return v;
 }
 
 // load that bypasses the vector L1 (sc1): for data this wavefront itself rewrote earlier in the
@@ -890,10 +824,6 @@ __device__ __forceinline__ uint32_t prefix_run(const Src& src, uint64_t p, uint6
 constexpr uint32_t kLongCap = 256;
 constexpr uint32_t kLongCap9 = 256;  // -9: pass 1 extends exactly up to this
 constexpr uint32_t kSatQ = 128;  // saturated-candidate queue per wavefront (flushed at 64)
-// broadcast chunk list: >= slots / 64 + number of groups of >= 64 slots (64 Ki slots with the LDS
-// window, 128 Ki otherwise)
-template <bool kLds>
-constexpr uint32_t kBigChunks = kLds ? 2048 : 4096;
 constexpr uint32_t kLongMatch = 0xFFFFFFFFu;
 constexpr uint32_t kBigGroup = 8192;  // -9: targets with more candidates go to k_find_big / k_find_long9
 constexpr uint32_t kBigRun = 2048;    // the same for a run key (vvvv) in blocks k_find_big takes
@@ -4260,6 +4190,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_lazy_walk(const Block* __re
       const uint32_t r3 = r2 + 1u + len2;
       const uint32_t l3 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((r3 < pc ? r3 : 0u) << 2), (int)sel);
       const bool in = lk && r2 < pc && r3 < pc;
+      // wave_path (sz4_device.h) written out: the lane indices are masked with & 63u here, which compiles differently
       uint32_t F[6];
       F[0] = in ? l3 : 64u;
 #pragma unroll
@@ -5708,23 +5639,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_walk(const Block* __restric
     if (mm == 0) {
       next = wbase + lim;  // literals carry the path out of the window (or to aNext)
     } else {
-      uint32_t F[6];
-      F[0] = lane + len < 64u ? lane + len : 64u;
-#pragma unroll
-      for (int k = 1; k < 6; k++) {
-        const uint32_t g = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(F[k - 1] << 2), (int)F[k - 1]);
-        F[k] = F[k - 1] >= 64u ? 64u : g;
-      }
-      uint32_t x = e;
-      {
-        const uint32_t y = rdlane(F[5], e);
-        x = y <= lane ? y : x;
-      }
-#pragma unroll
-      for (int k = 4; k >= 0; k--) {
-        const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(x << 2), (int)F[k]);
-        x = y <= lane ? y : x;
-      }
+      const uint32_t x = wave_path(lane + len < 64u ? lane + len : 64u, e, lane);
       const bool rec = x == lane && len > 1u && lane < lim;
       const uint64_t rb = __ballot(rec);
       const uint32_t cnt = (uint32_t)__builtin_popcountll(rb);

@@ -28,6 +28,10 @@
 //                   checks the assumptions per block (re-joining the wrong ones), k_unlz4_sub decodes every
 //                   sub-segment into a value-or-reference image, k_unlz4_pack resolves the references
 //
+//   One header walker, unlz4_walk<Walk>, parses tokens for all of them: Walk::kBlock in k_unlz4_sizes,
+//   Walk::kSpec in k_unlz4_spec, Walk::kJoin in un_join (k_unlz4_join, k_unlz4_fix).  The wave helpers
+//   (readlane, DPP scans and row sums, wave_path) are the shared ones of sz4_device.h.
+//
 // Byte work only: decoding one block is a chain of sequences (each match may read the bytes the one
 // before it wrote), so the parallelism is one wavefront per block (or per sub-segment in split mode) and
 // 64 bytes per copy step.
@@ -36,6 +40,7 @@
 
 #include <algorithm>
 
+#include "sz4_device.h"
 #include "sz4_internal.h"
 
 namespace sz4 {
@@ -51,11 +56,6 @@ __device__ uint64_t sz4_udiag[16];
 #endif
 
 namespace {
-
-__device__ __forceinline__ uint32_t un_rdlane(uint32_t v, uint32_t l)
-{
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
-}
 
 // 256 frame bytes [base, base + 256) held by the 64 lanes, 4 each; the cursor is wave-uniform
 struct Window {
@@ -77,7 +77,7 @@ struct Window {
   {
     if (c < base || c >= base + 192) fill(c, lane);
     const uint32_t r = (uint32_t)(c - base);
-    return (un_rdlane(w, r >> 2) >> (8 * (r & 3))) & 0xFFu;
+    return (rdlane(w, r >> 2) >> (8 * (r & 3))) & 0xFFu;
   }
 };
 
@@ -91,27 +91,6 @@ constexpr uint64_t kWaitLimit = 100000000ull * 60;  // 60 s of s_memrealtime (10
 constexpr uint32_t kRing = 16384;
 constexpr uint32_t kSync = kRing / 2;
 
-// v_writelane (the LLVM intrinsic by name): lane `l` of v becomes the uniform `x`
-extern "C" __device__ int sz4_un_writelane(int, int, int) __asm("llvm.amdgcn.writelane.i32");
-__device__ __forceinline__ uint32_t un_wrlane(uint32_t v, uint32_t x, uint32_t l)
-{
-  return (uint32_t)sz4_un_writelane((int)x, (int)l, (int)v);
-}
-
-// inclusive add-scan over the 64 lanes by DPP (row shifts 1, 2, 4, 8, then the row broadcasts): six
-// dependent VALU steps instead of six ds_bpermute round trips
-__device__ __forceinline__ uint32_t un_incl_scan_add(uint32_t v, uint32_t lane)
-{
-  (void)lane;
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);  // row_shr:1
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);  // row_shr:2
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);  // row_shr:4
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);  // row_shr:8
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast:15
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);  // row_bcast:31
-  return v;
-}
-
 // Sequence list of block bi: at most len/3 + 2 entries (a sequence with a match takes >= 3 frame
 // bytes), at seqAll + src/3 + 2 * bi -- disjoint from every other block's, no host prefix needed.
 __device__ __forceinline__ uint4* seq_base(uint4* seqAll, const UnBlock& B, uint32_t bi)
@@ -122,24 +101,33 @@ __device__ __forceinline__ uint32_t seq_cap(const UnBlock& B) { return B.len / 3
 
 // Header walk of one block (smallz4cat.c:212-323) from block-relative frame offset r0: its decoded
 // length, or kNone when it is malformed the way oz_unlz4 rejects it (a length byte, literal run or
-// offset running past the block, offset 0).  Every sequence is recorded as (literals, match length,
-// offset, frame offset of the literals from B.src): lane l holds entry (count & ~63) + l until 64 are
-// complete, then one coalesced store.  The whole block: r0 = 0, stop = B.len.  A split block's
-// sub-segment (below): the walk stops at its first token start >= stop (W.exit) and, with kMark, sets
-// bit (token start - mb) of the LDS mask for every sequence it parsed; with kMerge, it stops before a
-// token start whose bit is set in that LDS mask (W.merged: the speculative walk of the sub-segment
-// parsed from there on already).  With kMark, cum (when given) receives each recorded sequence's output
-// offset from r0 (the bytes the sequences before it decode), stored like seq.
+// offset running past the block, offset 0).  Every sequence is recorded in seq as (literals, match
+// length, offset, frame offset of the literals from B.src).
+//   kBlock  the whole block (k_unlz4_sizes): r0 = 0, stop = B.len; neither maskLds nor cum is touched
+//   kSpec   a split block's sub-segment from its first byte (k_unlz4_spec): the walk stops at its first
+//           token start >= stop (W.exit), sets bit (token start - mb) of the LDS mask for every sequence it
+//           recorded, and cum receives each recorded sequence's output offset from r0 (the bytes the
+//           sequences before it decode), stored like seq
+//   kJoin   a sub-segment from an entry of the true chain (un_join): the walk also stops before a token
+//           start whose bit is set in the LDS mask (W.merged: the speculative walk of the sub-segment
+//           parsed from there on already); the mask is read-only while a join walks
+// The token chain is followed 64 window positions at a time on the vector unit: lane l takes the
+// pre-decoded header at window position 64 s + l and steps to l + 3 + literals (+ 1 for a match-length
+// byte) -- 64 when that is out of the sub-window or the header needs the byte-wise path --, and wave_path
+// gives every lane the last token start at or below itself.  The lanes that find themselves are the
+// sequences in this sub-window: stored by mbcnt rank, their decoded bytes summed by a row reduction (kSpec:
+// by the scan that also yields cum).
+enum class Walk { kBlock, kSpec, kJoin };
 struct WalkEnd {
   uint32_t exit;    // block-relative frame offset where the walk stopped
   uint32_t ns;      // sequences recorded
   uint32_t merged;  // 1: stopped at a merge bit (exit is that token start)
   uint32_t end;     // 1: reached the block end
 };
-template <bool kMark, bool kMerge>
+template <Walk kMode>
 __device__ uint64_t unlz4_walk(const uint8_t* __restrict__ f, uint64_t n, const UnBlock& B, uint32_t lane, uint32_t r0,
-                               uint32_t stop, uint4* __restrict__ seq, uint32_t cap, uint32_t* maskLds, uint32_t mb,
-                               WalkEnd& W, uint32_t* __restrict__ cum = nullptr)
+                               uint32_t stop, uint4* __restrict__ seq, uint32_t cap, WalkEnd& W,
+                               uint32_t* maskLds = nullptr, uint32_t mb = 0, uint32_t* __restrict__ cum = nullptr)
 {
   W = WalkEnd{r0, 0u, 0u, 0u};
   if (B.stored) {  // uncompressed block (smallz4cat.c:329-343)
@@ -150,33 +138,26 @@ __device__ uint64_t unlz4_walk(const uint8_t* __restrict__ f, uint64_t n, const 
   const uint64_t end = B.src + B.len;
   uint64_t r = B.src + r0, w = 0;  // frame cursor; bytes decoded so far
   uint32_t ns = 0;
-  uint4 buf = make_uint4(0u, 0u, 0u, 0u);
-  uint32_t bufc = 0;
   // before: the bytes decoded from r0 up to this sequence
-  auto push = [&](uint32_t tok, uint32_t lits, uint32_t ml, uint32_t off, uint32_t frel, uint32_t before) {
-    const uint32_t l = ns & 63u;
-    if constexpr (kMark) {
-      if (lane == 0) atomicOr(&maskLds[(tok - mb) >> 5], 1u << ((tok - mb) & 31));
-      bufc = un_wrlane(bufc, before, l);
+  auto push = [&](uint32_t tokAt, uint32_t lits, uint32_t ml, uint32_t off, uint32_t frel, uint32_t before) {
+    if (lane == 0) {
+      seq[ns] = make_uint4(lits, ml, off, frel);
+      if constexpr (kMode == Walk::kSpec) {
+        atomicOr(&maskLds[(tokAt - mb) >> 5], 1u << ((tokAt - mb) & 31));
+        if (cum) cum[ns] = before;
+      }
     }
-    buf.x = un_wrlane(buf.x, lits, l);
-    buf.y = un_wrlane(buf.y, ml, l);
-    buf.z = un_wrlane(buf.z, off, l);
-    buf.w = un_wrlane(buf.w, frel, l);
     ns++;
-    if ((ns & 63u) == 0u) {
-      seq[ns - 64u + lane] = buf;
-      if (kMark && cum) cum[ns - 64u + lane] = bufc;
-    }
   };
   auto merge_at = [&](uint32_t tok) -> bool {
-    if constexpr (kMerge) return (maskLds[(tok - mb) >> 5] >> ((tok - mb) & 31)) & 1u;
+    if constexpr (kMode == Walk::kJoin) return (maskLds[(tok - mb) >> 5] >> ((tok - mb) & 31)) & 1u;
     return false;
   };
   Window win{f, n, 0, 0};
   // One sequence byte by byte through the window (smallz4cat.c:212-323): 0 next, 1 block done, 2 malformed.
   // Taken for what the pre-decoded headers below do not cover: extended literal runs, match lengths
-  // with more than one extension byte, headers reaching past the register window.
+  // with more than one extension byte, headers reaching past the register window, the block's last 20
+  // bytes.  Every mode goes through it, so they agree on every frame, malformed ones included.
   auto one_seq = [&]() -> int {
     const uint32_t tokAt = (uint32_t)(r - B.src);
     const uint32_t tok = win.byte(r++, lane);
@@ -216,25 +197,20 @@ __device__ uint64_t unlz4_walk(const uint8_t* __restrict__ f, uint64_t n, const 
   };
   // A sequence starting 20 or more bytes before the block end passes every bounds check of one_seq
   // (its header reads at most 18 bytes past the token, its literals end before the block does), so the
-  // walk below checks nothing but a zero offset and runs on block-relative 32-bit cursors.
-  const uint32_t fastEnd = min(B.len > 20u ? B.len - 20u : 0u, stop);
-  while (r < end && (uint32_t)(r - B.src) < stop) {
-    if (kMerge && merge_at((uint32_t)(r - B.src))) {
+  // window walk below checks nothing but a zero offset and runs on block-relative 32-bit cursors.
+  // A whole block's stop is its end, which `r < end` tests: only a sub-segment compares against stop.
+  const uint32_t toEnd = B.len > 20u ? B.len - 20u : 0u;
+  const uint32_t fastEnd = kMode != Walk::kBlock ? min(toEnd, stop) : toEnd;
+  bool done = false;
+  while (r < end && (kMode == Walk::kBlock || (uint32_t)(r - B.src) < stop)) {
+    if (merge_at((uint32_t)(r - B.src))) {
       W.merged = 1;
       break;
     }
     // Pre-decode a header at every window position q = 4 lane + k: token | offset << 8 | extension
     // byte << 24, or ~0 when the header needs the byte-wise path (literal run >= 15, a second match
-    // extension byte, or bytes past the register window).  The walk costs one readlane per sequence.
+    // extension byte, bytes past the register window) or is malformed (offset 0: one_seq rejects it).
     win.fill(r, lane);
-    // kMerge: the mask words this window can reach, one per lane (a token start's merge bit by readlane, not
-    // one dependent LDS read per sequence); the mask is read-only while a join walks
-    uint32_t mw = 0, mw0 = 0;
-    if constexpr (kMerge) {
-      mw0 = (uint32_t)(r - B.src - mb) >> 5;
-      const uint32_t wi = mw0 + lane;
-      mw = lane < 8u && wi < kUnSub / 32u ? maskLds[wi] : 0u;
-    }
     uint32_t cand[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -246,163 +222,11 @@ __device__ uint64_t unlz4_walk(const uint8_t* __restrict__ f, uint64_t n, const 
       const uint32_t v = (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * (a & 3u)));
       const bool ext = (tok & 15u) == 15u;
       const uint32_t last = a + 1u + (ext ? 1u : 0u);  // last window byte the header reads
-      const bool ok = (tok >> 4) != 15u && last < 256u && !(ext && ((v >> 16) & 0xFFu) == 255u);
+      const bool ok = (tok >> 4) != 15u && last < 256u && !(ext && ((v >> 16) & 0xFFu) == 255u) && (v & 0xFFFFu) != 0u;
       cand[k] = ok ? (tok | (v << 8)) : 0xFFFFFFFFu;  // v's bytes 0-2: offset, extension byte
     }
     const uint32_t wb = (uint32_t)(win.base - B.src);  // window base, block-relative (r >= B.src >= base - 3)
     uint32_t rr = (uint32_t)(r - B.src);
-    bool slow = false, stopped = false;
-    while (rr < fastEnd) {
-      if (kMerge && rr != (uint32_t)(r - B.src) &&
-          ((un_rdlane(mw, ((rr - mb) >> 5) - mw0) >> ((rr - mb) & 31u)) & 1u)) {
-        stopped = true;
-        break;
-      }
-      const uint32_t q = rr - wb;
-      if (q >= 192u) break;
-      const uint32_t ql = q >> 2;
-      const uint32_t c0 = un_rdlane(cand[0], ql), c1 = un_rdlane(cand[1], ql);
-      const uint32_t c2 = un_rdlane(cand[2], ql), c3 = un_rdlane(cand[3], ql);
-      const uint32_t pk = (q & 2u) ? ((q & 1u) ? c3 : c2) : ((q & 1u) ? c1 : c0);
-      if (pk == 0xFFFFFFFFu) {
-        slow = q < 64u;  // else refill at rr first: the header may fit the next window
-        break;
-      }
-      const uint32_t off = (pk >> 8) & 0xFFFFu;
-      if (off == 0) {  // "invalid offset" (smallz4cat.c:265-267)
-        W.exit = rr;
-        return kNone;
-      }
-      const uint32_t lits = (pk >> 4) & 15u, nib = pk & 15u;
-      const uint32_t ml = kMinMatch + nib + (nib == 15u ? pk >> 24 : 0u);
-      push(rr, lits, ml, off, rr + 1u, (uint32_t)w);
-      w += lits + ml;
-      rr += 3u + lits + (nib == 15u ? 1u : 0u);
-    }
-    r = B.src + rr;
-    if (stopped) continue;  // the loop head sees the merge bit
-    if (rr < fastEnd && !slow) continue;  // refill
-    // byte-wise: a header the window could not pre-decode, or the block's last 20 bytes
-    if (r >= end || rr >= stop) break;
-    if (kMerge && merge_at(rr)) {
-      W.merged = 1;
-      break;
-    }
-    if (ns >= cap) {  // cannot happen in a well-formed block
-      W.exit = rr;
-      return kNone;
-    }
-    const int e = one_seq();
-    if (e == 2) {
-      W.exit = rr;
-      return kNone;
-    }
-    if (e == 1) break;
-  }
-  if (ns & 63u) {
-    const uint32_t b = ns & ~63u;
-    if (lane < (ns & 63u)) {
-      seq[b + lane] = buf;
-      if (kMark && cum) cum[b + lane] = bufc;
-    }
-  }
-  W.exit = (uint32_t)(r - B.src);
-  W.ns = ns;
-  W.end = r >= end ? 1u : 0u;
-  return w;
-}
-
-
-// every lane receives the sum of its 16-lane row
-__device__ __forceinline__ uint32_t un_row_sum(uint32_t v)
-{
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false);  // row_half_mirror
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false);  // row_mirror
-  return v;
-}
-
-// unlz4_walk over a whole block (k_unlz4_sizes) with the token chain followed 64 window positions at a
-// time on the vector unit: lane l takes the pre-decoded header at window position 64 s + l, steps to
-// l + 3 + literals (+ 1 for a match-length byte) -- F1, 64 = out of the sub-window, or 64 where the
-// header needs the byte-wise path --, F2 .. F32 by doubling (ds_bpermute), and every lane finds the last
-// token start at or below itself by binary lifting from the entry.  The lanes that find themselves are
-// the block's sequences in this sub-window: stored by mbcnt rank, their decoded bytes summed by a row
-// reduction.  Whatever the pre-decoded headers do not cover goes through the same byte-wise sequence
-// as unlz4_walk, so the two agree on every frame, malformed ones included.
-__device__ uint64_t unlz4_walk_vec(const uint8_t* __restrict__ f, uint64_t n, const UnBlock& B, uint32_t lane,
-                                   uint4* __restrict__ seq, uint32_t cap, WalkEnd& W)
-{
-  W = WalkEnd{0u, 0u, 0u, 0u};
-  if (B.stored) {
-    W.exit = B.len;
-    W.end = 1;
-    return B.len;
-  }
-  const uint64_t end = B.src + B.len;
-  uint64_t r = B.src, w = 0;
-  uint32_t ns = 0;
-  auto push = [&](uint32_t lits, uint32_t ml, uint32_t off, uint32_t frel) {
-    if (lane == 0) seq[ns] = make_uint4(lits, ml, off, frel);
-    ns++;
-  };
-  Window win{f, n, 0, 0};
-  auto one_seq = [&]() -> int {
-    const uint32_t tok = win.byte(r++, lane);
-    uint64_t lits = tok >> 4;
-    if (lits == 15) {
-      uint32_t x;
-      do {
-        if (r >= end) return 2;
-        x = win.byte(r++, lane);
-        lits += x;
-      } while (x == 255);
-    }
-    if (r + lits > end) return 2;
-    const uint32_t frel = (uint32_t)(r - B.src);
-    w += lits;
-    r += lits;
-    if (r == end) {  // the last sequence has literals only
-      push((uint32_t)lits, 0u, 0u, frel);
-      return 1;
-    }
-    if (r + 2 > end) return 2;
-    const uint32_t off = win.byte(r, lane) | (win.byte(r + 1, lane) << 8);
-    r += 2;
-    if (off == 0) return 2;  // "invalid offset" (smallz4cat.c:265-267)
-    uint64_t ml = kMinMatch + (tok & 15);
-    if (ml == kMinMatch + 15) {
-      uint32_t x;
-      do {
-        if (r >= end) return 2;
-        x = win.byte(r++, lane);
-        ml += x;
-      } while (x == 255);
-    }
-    push((uint32_t)lits, (uint32_t)ml, off, frel);
-    w += ml;
-    return 0;
-  };
-  const uint32_t fastEnd = B.len > 20u ? B.len - 20u : 0u;
-  while (r < end) {
-    win.fill(r, lane);
-    uint32_t cand[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const uint32_t tok = (win.w >> (8 * k)) & 0xFFu;
-      const uint32_t a = 4u * lane + (uint32_t)k + 1u + (tok >> 4);  // window index of the offset
-      const uint32_t ia = (a >> 2) << 2;
-      const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)ia, (int)win.w);
-      const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(ia + 4u), (int)win.w);
-      const uint32_t v = (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * (a & 3u)));
-      const bool ext = (tok & 15u) == 15u;
-      const uint32_t last = a + 1u + (ext ? 1u : 0u);  // last window byte the header reads
-      const bool ok = (tok >> 4) != 15u && last < 256u && !(ext && ((v >> 16) & 0xFFu) == 255u) && (v & 0xFFFFu) != 0u;
-      cand[k] = ok ? (tok | (v << 8)) : 0xFFFFFFFFu;  // v's bytes 0-2: offset, extension byte
-    }
-    const uint32_t wb = (uint32_t)(win.base - B.src);  // window base, block-relative
-    uint32_t rr = (uint32_t)(r - B.src);
     bool slow = false, bad = false;
     while (rr < fastEnd) {
       const uint32_t q0 = rr - wb;
@@ -418,208 +242,23 @@ __device__ uint64_t unlz4_walk_vec(const uint8_t* __restrict__ f, uint64_t n, co
       const bool ok = c != 0xFFFFFFFFu && pos < fastEnd;
       const uint32_t lits = (c >> 4) & 15u, nib = c & 15u;
       const uint32_t step = 3u + lits + (nib == 15u ? 1u : 0u);
-      uint32_t F[6];
-      F[0] = ok && lane + step < 64u ? lane + step : 64u;
-#pragma unroll
-      for (int k = 1; k < 6; k++) {
-        const uint32_t g = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(F[k - 1] << 2), (int)F[k - 1]);
-        F[k] = F[k - 1] >= 64u ? 64u : g;
+      const uint32_t x = wave_path(ok && lane + step < 64u ? lane + step : 64u, e, lane);
+      // tok: a token start of the path whose pre-decoded header is recorded here (the path's last one may
+      // need the byte-wise path).  x == lane alone says "on the path": a lane below e receives e (wave_path).
+      bool tok = x == lane && ok;
+      // A sub-segment: the path's first token start at or past stop, or with its merge bit set, ends the walk
+      // (positions >= stop are not ok, so such a token is the path's last).  Not in a whole block: stop = B.len
+      // >= fastEnd + 20, and a pre-decoded step of at most 18 bytes from below fastEnd cannot carry the path there.
+      uint64_t term = 0;
+      uint32_t T = 64;
+      if constexpr (kMode != Walk::kBlock) {
+        const bool onPath = x == lane && lane >= e;  // `lane >= e` only restates x == lane, see above
+        const uint32_t mrel = pos - mb;
+        const bool mbit = kMode == Walk::kJoin && pos < stop && mrel < kUnSub && ((maskLds[mrel >> 5] >> (mrel & 31u)) & 1u);
+        term = __ballot(onPath && (pos >= stop || mbit));
+        T = term ? (uint32_t)__builtin_ctzll(term) : 64u;
+        tok = onPath && ok && lane < T;
       }
-      uint32_t x = e;
-      {
-        const uint32_t y = un_rdlane(F[5], e);
-        x = y <= lane ? y : x;
-      }
-#pragma unroll
-      for (int k = 4; k >= 0; k--) {
-        const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(x << 2), (int)F[k]);
-        x = y <= lane ? y : x;
-      }
-      const bool tok = x == lane && ok;
-      const uint64_t tb = __ballot(tok);
-      const uint32_t cnt = (uint32_t)__builtin_popcountll(tb);
-      if (ns + cnt > cap) {  // cannot happen in a well-formed block
-        bad = true;
-        break;
-      }
-      const uint32_t ml = kMinMatch + nib + (nib == 15u ? c >> 24 : 0u);
-      if (tok) {
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(tb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tb, 0u));
-        seq[ns + rank] = make_uint4(lits, ml, (c >> 8) & 0xFFFFu, pos + 1u);
-      }
-      ns += cnt;
-      const uint32_t rs = un_row_sum(tok ? lits + ml : 0u);
-      w += (uint64_t)(un_rdlane(rs, 0) + un_rdlane(rs, 16) + un_rdlane(rs, 32) + un_rdlane(rs, 48));
-      const uint32_t p = un_rdlane(x, 63);  // the last token start of the path in this sub-window
-      if (!((__ballot(ok) >> p) & 1ull)) {
-        // a header the window did not pre-decode: from a refilled window, or byte-wise at the window start
-        rr = wb + sb + p;
-        slow = sb + p < 64u;
-        break;
-      }
-      rr = wb + sb + p + un_rdlane(step, p);
-    }
-    if (bad) {
-      W.exit = rr;
-      return kNone;
-    }
-    r = B.src + rr;
-    if (rr < fastEnd && !slow) continue;  // refill
-    if (r >= end) break;
-    if (ns >= cap) {
-      W.exit = rr;
-      return kNone;
-    }
-    const int e = one_seq();
-    if (e == 2) {
-      W.exit = (uint32_t)(r - B.src);
-      return kNone;
-    }
-    if (e == 1) break;
-  }
-  W.exit = (uint32_t)(r - B.src);
-  W.ns = ns;
-  W.end = r >= end ? 1u : 0u;
-  return w;
-}
-
-// unlz4_walk<kMark, kMerge> of a sub-segment on the vector unit, as unlz4_walk_vec: the path through 64
-// window positions at a time by binary lifting.  kMerge (a join): its first token start at or past stop or
-// with its bit set in the read-only LDS mask ends the walk there (W.merged).  kMark (the speculative walk):
-// the path's token starts are OR-ed into the mask 64 window positions at a time (one ballot), and cum
-// receives each sequence's output offset from r0.  Whatever the pre-decoded headers do not cover goes
-// byte-wise, as in unlz4_walk, so the two agree on every frame.
-template <bool kMark, bool kMerge>
-__device__ uint64_t unlz4_walk_v(const uint8_t* __restrict__ f, uint64_t n, const UnBlock& B, uint32_t lane,
-                                 uint32_t r0, uint32_t stop, uint4* __restrict__ seq, uint32_t cap, uint32_t* maskLds,
-                                 uint32_t mb, WalkEnd& W, uint32_t* __restrict__ cum = nullptr)
-{
-  W = WalkEnd{r0, 0u, 0u, 0u};
-  if (B.stored) {
-    W.exit = B.len;
-    W.end = 1;
-    return B.len;
-  }
-  const uint64_t end = B.src + B.len;
-  uint64_t r = B.src + r0, w = 0;
-  uint32_t ns = 0;
-  auto push = [&](uint32_t tokAt, uint32_t lits, uint32_t ml, uint32_t off, uint32_t frel, uint32_t before) {
-    if (lane == 0) {
-      seq[ns] = make_uint4(lits, ml, off, frel);
-      if constexpr (kMark) {
-        atomicOr(&maskLds[(tokAt - mb) >> 5], 1u << ((tokAt - mb) & 31));
-        if (cum) cum[ns] = before;
-      }
-    }
-    ns++;
-  };
-  auto merge_at = [&](uint32_t tok) -> bool {
-    if constexpr (kMerge) return (maskLds[(tok - mb) >> 5] >> ((tok - mb) & 31)) & 1u;
-    return false;
-  };
-  Window win{f, n, 0, 0};
-  auto one_seq = [&]() -> int {
-    const uint32_t tokAt = (uint32_t)(r - B.src);
-    const uint32_t tok = win.byte(r++, lane);
-    uint64_t lits = tok >> 4;
-    if (lits == 15) {
-      uint32_t x;
-      do {
-        if (r >= end) return 2;
-        x = win.byte(r++, lane);
-        lits += x;
-      } while (x == 255);
-    }
-    if (r + lits > end) return 2;
-    const uint32_t frel = (uint32_t)(r - B.src);
-    w += lits;
-    r += lits;
-    if (r == end) {  // the last sequence has literals only
-      push(tokAt, (uint32_t)lits, 0u, 0u, frel, (uint32_t)(w - lits));
-      return 1;
-    }
-    if (r + 2 > end) return 2;
-    const uint32_t off = win.byte(r, lane) | (win.byte(r + 1, lane) << 8);
-    r += 2;
-    if (off == 0) return 2;  // "invalid offset" (smallz4cat.c:265-267)
-    uint64_t ml = kMinMatch + (tok & 15);
-    if (ml == kMinMatch + 15) {
-      uint32_t x;
-      do {
-        if (r >= end) return 2;
-        x = win.byte(r++, lane);
-        ml += x;
-      } while (x == 255);
-    }
-    push(tokAt, (uint32_t)lits, (uint32_t)ml, off, frel, (uint32_t)(w - lits));
-    w += ml;
-    return 0;
-  };
-  const uint32_t fastEnd = min(B.len > 20u ? B.len - 20u : 0u, stop);
-  bool done = false;
-  while (r < end && (uint32_t)(r - B.src) < stop) {
-    if (kMerge && merge_at((uint32_t)(r - B.src))) {
-      W.merged = 1;
-      break;
-    }
-    win.fill(r, lane);
-    uint32_t cand[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const uint32_t tok = (win.w >> (8 * k)) & 0xFFu;
-      const uint32_t a = 4u * lane + (uint32_t)k + 1u + (tok >> 4);  // window index of the offset
-      const uint32_t ia = (a >> 2) << 2;
-      const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)ia, (int)win.w);
-      const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(ia + 4u), (int)win.w);
-      const uint32_t v = (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * (a & 3u)));
-      const bool ext = (tok & 15u) == 15u;
-      const uint32_t last = a + 1u + (ext ? 1u : 0u);  // last window byte the header reads
-      const bool ok = (tok >> 4) != 15u && last < 256u && !(ext && ((v >> 16) & 0xFFu) == 255u) && (v & 0xFFFFu) != 0u;
-      cand[k] = ok ? (tok | (v << 8)) : 0xFFFFFFFFu;  // v's bytes 0-2: offset, extension byte
-    }
-    const uint32_t wb = (uint32_t)(win.base - B.src);  // window base, block-relative
-    uint32_t rr = (uint32_t)(r - B.src);
-    bool slow = false, bad = false;
-    while (rr < fastEnd) {
-      const uint32_t q0 = rr - wb;
-      if (q0 >= 192u) break;  // refill
-      const uint32_t sb = q0 & ~63u, e = q0 & 63u;
-      const int src = (int)(((sb >> 2) + (lane >> 2)) << 2);
-      const uint32_t g0 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)cand[0]);
-      const uint32_t g1 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)cand[1]);
-      const uint32_t g2 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)cand[2]);
-      const uint32_t g3 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)cand[3]);
-      const uint32_t c = (lane & 2u) ? ((lane & 1u) ? g3 : g2) : ((lane & 1u) ? g1 : g0);
-      const uint32_t pos = wb + sb + lane;  // block-relative frame offset of this lane's token
-      const bool ok = c != 0xFFFFFFFFu && pos < fastEnd;
-      const uint32_t lits = (c >> 4) & 15u, nib = c & 15u;
-      const uint32_t step = 3u + lits + (nib == 15u ? 1u : 0u);
-      uint32_t F[6];
-      F[0] = ok && lane + step < 64u ? lane + step : 64u;
-#pragma unroll
-      for (int k = 1; k < 6; k++) {
-        const uint32_t g = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(F[k - 1] << 2), (int)F[k - 1]);
-        F[k] = F[k - 1] >= 64u ? 64u : g;
-      }
-      uint32_t x = e;
-      {
-        const uint32_t y = un_rdlane(F[5], e);
-        x = y <= lane ? y : x;
-      }
-#pragma unroll
-      for (int k = 4; k >= 0; k--) {
-        const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(x << 2), (int)F[k]);
-        x = y <= lane ? y : x;
-      }
-      // the path's token starts in this sub-window (its last one may need the byte-wise path); the first of
-      // them at or past stop, or with its merge bit set, ends the walk (positions >= stop are not ok, so
-      // such a token is the path's last)
-      const bool onPath = x == lane && lane >= e;
-      const uint32_t mrel = pos - mb;
-      const bool mbit = kMerge && pos < stop && mrel < kUnSub && ((maskLds[mrel >> 5] >> (mrel & 31u)) & 1u);
-      const uint64_t term = __ballot(onPath && (pos >= stop || mbit));
-      const uint32_t T = term ? (uint32_t)__builtin_ctzll(term) : 64u;
-      const bool tok = onPath && ok && lane < T;
       const uint64_t tb = __ballot(tok);
       const uint32_t cnt = (uint32_t)__builtin_popcountll(tb);
       if (ns + cnt > cap) {  // cannot happen in a well-formed block
@@ -629,13 +268,13 @@ __device__ uint64_t unlz4_walk_v(const uint8_t* __restrict__ f, uint64_t n, cons
       const uint32_t ml = kMinMatch + nib + (nib == 15u ? c >> 24 : 0u);
       const uint32_t dec = tok ? lits + ml : 0u;
       uint32_t incl = 0;
-      if constexpr (kMark) incl = un_incl_scan_add(dec, lane);
+      if constexpr (kMode == Walk::kSpec) incl = wave_incl_scan_add(dec);
       if (tok) {
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(tb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tb, 0u));
         seq[ns + rank] = make_uint4(lits, ml, (c >> 8) & 0xFFFFu, pos + 1u);
-        if (kMark && cum) cum[ns + rank] = (uint32_t)w + incl - dec;
+        if (kMode == Walk::kSpec && cum) cum[ns + rank] = (uint32_t)w + incl - dec;
       }
-      if constexpr (kMark) {
+      if constexpr (kMode == Walk::kSpec) {
         // the recorded token starts' bits: 64 consecutive positions from wb + sb (those below mb are none)
         if (tb && lane == 0) {
           int32_t m0 = (int32_t)(wb + sb) - (int32_t)mb;
@@ -653,11 +292,11 @@ __device__ uint64_t unlz4_walk_v(const uint8_t* __restrict__ f, uint64_t n, cons
         }
       }
       ns += cnt;
-      if constexpr (kMark) {
-        w += un_rdlane(incl, 63);
+      if constexpr (kMode == Walk::kSpec) {
+        w += rdlane(incl, 63);
       } else {
-        const uint32_t rs = un_row_sum(dec);
-        w += (uint64_t)(un_rdlane(rs, 0) + un_rdlane(rs, 16) + un_rdlane(rs, 32) + un_rdlane(rs, 48));
+        const uint32_t rs = row_sum(dec);
+        w += (uint64_t)(rdlane(rs, 0) + rdlane(rs, 16) + rdlane(rs, 32) + rdlane(rs, 48));
       }
       if (term) {
         rr = wb + sb + T;
@@ -665,14 +304,15 @@ __device__ uint64_t unlz4_walk_v(const uint8_t* __restrict__ f, uint64_t n, cons
         done = true;
         break;
       }
-      const uint32_t p = un_rdlane(x, 63);  // the last token start of the path in this sub-window
+      const uint32_t p = rdlane(x, 63);  // the last token start of the path in this sub-window
       if (!((__ballot(ok) >> p) & 1ull)) {
-        // a header the window did not pre-decode: from a refilled window, or byte-wise at the window start
+        // a header the window did not pre-decode: refill at the token first (the header may fit the next
+        // window), byte-wise only when the token is already in the window's first 64 bytes
         rr = wb + sb + p;
         slow = sb + p < 64u;
         break;
       }
-      rr = wb + sb + p + un_rdlane(step, p);
+      rr = wb + sb + p + rdlane(step, p);
     }
     if (bad) {
       W.exit = rr;
@@ -681,12 +321,13 @@ __device__ uint64_t unlz4_walk_v(const uint8_t* __restrict__ f, uint64_t n, cons
     r = B.src + rr;
     if (done) break;
     if (rr < fastEnd && !slow) continue;  // refill
-    if (r >= end || rr >= stop) break;
-    if (kMerge && merge_at(rr)) {
+    // byte-wise: a header the window could not pre-decode, or the block's last 20 bytes
+    if (r >= end || (kMode != Walk::kBlock && rr >= stop)) break;
+    if (merge_at(rr)) {
       W.merged = 1;
       break;
     }
-    if (ns >= cap) {
+    if (ns >= cap) {  // cannot happen in a well-formed block
       W.exit = rr;
       return kNone;
     }
@@ -730,12 +371,12 @@ __device__ uint64_t unlz4_decode(const uint8_t* __restrict__ f, uint64_t n, cons
     const uint4 q = lane < cnt ? seq[b0 + lane] : make_uint4(0u, 0u, 0u, 0u);
     // output offset of every sequence's literals (a wavefront scan of literals + match length)
     const uint32_t tot = q.x + q.y;
-    const uint32_t incl = un_incl_scan_add(tot, lane);
+    const uint32_t incl = wave_incl_scan_add(tot);
     const uint64_t pos = w + (incl - tot);
     // the frame bytes of the 64 sequences' literals in registers when they span <= 512 bytes: lane l
     // holds [fb + 8l, fb + 8l + 8)
-    const uint64_t fb = (B.src + un_rdlane(q.w, 0)) & ~7ull;
-    const uint64_t fe = B.src + un_rdlane(q.w + q.x, cnt - 1u);
+    const uint64_t fb = (B.src + rdlane(q.w, 0)) & ~7ull;
+    const uint64_t fe = B.src + rdlane(q.w + q.x, cnt - 1u);
     const bool inWin = fe - fb <= 512u;
     uint32_t w0 = 0, w1 = 0;
     if (inWin) {
@@ -754,8 +395,8 @@ __device__ uint64_t unlz4_decode(const uint8_t* __restrict__ f, uint64_t n, cons
       }
     }
     for (uint32_t j = 0; j < cnt; j++) {
-      const uint32_t L = un_rdlane(q.x, j), M = un_rdlane(q.y, j), off = un_rdlane(q.z, j), fr = un_rdlane(q.w, j);
-      const uint64_t P = B.dst + (uint64_t)un_rdlane((uint32_t)pos, j);  // a block decodes to < 2^32 bytes
+      const uint32_t L = rdlane(q.x, j), M = rdlane(q.y, j), off = rdlane(q.z, j), fr = rdlane(q.w, j);
+      const uint64_t P = B.dst + (uint64_t)rdlane((uint32_t)pos, j);  // a block decodes to < 2^32 bytes
       if (L) {
         if (inWin && L <= 64u) {
           // lane k takes byte k out of the register window
@@ -829,23 +470,11 @@ __device__ uint64_t unlz4_decode(const uint8_t* __restrict__ f, uint64_t n, cons
         }
       }
     }
-    w += un_rdlane(incl, cnt - 1u);
+    w += rdlane(incl, cnt - 1u);
   }
   return w;
 }
 
-
-// inclusive max-scan over the 64 lanes (rows by DPP shifts, then the row broadcasts)
-__device__ __forceinline__ uint32_t un_scan_max(uint32_t v)
-{
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false));  // row_shr:1
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false));  // row_shr:2
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false));  // row_shr:4
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false));  // row_shr:8
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false));  // row_bcast:15
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false));  // row_bcast:31
-  return v;
-}
 
 // Block bi's sequence list replayed 64 OUTPUT bytes per step instead of one sequence per step: for an
 // output window [W, W + 64) the sequences starting in it mark their first byte (an LDS slot per byte),
@@ -874,9 +503,9 @@ __device__ uint64_t unlz4_decode_vec(const uint8_t* __restrict__ f, uint64_t n, 
     const uint32_t cnt = B.nseq - b0 < 64u ? B.nseq - b0 : 64u;
     const uint4 q = lane < cnt ? seq[b0 + lane] : make_uint4(0u, 0u, 0u, 0u);
     const uint32_t tot = q.x + q.y;
-    const uint32_t incl = un_incl_scan_add(tot, lane);
+    const uint32_t incl = wave_incl_scan_add(tot);
     const uint32_t pj = incl - tot;  // batch-relative output offset of sequence `lane`
-    const uint32_t blen = un_rdlane(incl, cnt - 1u);
+    const uint32_t blen = rdlane(incl, cnt - 1u);
     // a match reading below the block start, or a sequence of no bytes: the sequence-wise decoder
     const bool far = lane < cnt && q.y != 0u && w + pj + q.x < (uint64_t)q.z;
     if (__ballot(far || (lane < cnt && tot == 0u))) {
@@ -898,9 +527,9 @@ __device__ uint64_t unlz4_decode_vec(const uint8_t* __restrict__ f, uint64_t n, 
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       const uint32_t mark = slot[lane];
       slot[lane] = 0;
-      const uint32_t sc = un_scan_max(mark);
+      const uint32_t sc = wave_incl_scan_max(mark);
       const uint32_t jj = (sc ? sc : jc) - 1u;  // this lane's sequence
-      jc = un_rdlane(sc ? sc : jc, 63);
+      jc = rdlane(sc ? sc : jc, 63);
       const uint32_t o = W + lane;  // batch-relative output byte
       const bool valid = o < blen;
       const int addr = (int)(jj << 2);
@@ -1273,6 +902,7 @@ __global__ __launch_bounds__(1024) void k_unlz4_ix_walk(const uint8_t* __restric
       const uint64_t ci = (uint64_t)e + lane;
       const uint32_t val = ci < M ? (inLds ? s_link[ci] : link[ci]) : kIxBad;
       const uint32_t nl = val < (uint32_t)M && (uint64_t)val < (uint64_t)e + 64 ? val - e : 64u;
+      // wave_path (sz4_device.h) written out: at() clamps the index, and the entry is always lane 0
       uint32_t J[6];
       J[0] = nl;
 #pragma unroll
@@ -1285,7 +915,7 @@ __global__ __launch_bounds__(1024) void k_unlz4_ix_walk(const uint8_t* __restric
       }
       const uint64_t path = __ballot(pos == lane);  // lane 0 is on it
       const uint32_t last = 63u - (uint32_t)__builtin_clzll(path);
-      const uint32_t exitv = un_rdlane(val, last);
+      const uint32_t exitv = rdlane(val, last);
       // the path's nodes are blocks, except a last node that ends the chain (END) or cannot be followed (BAD)
       const uint64_t blocks = exitv == kIxEnd || exitv == kIxBad ? path & ~(1ull << last) : path;
       const uint32_t cnt = (uint32_t)__builtin_popcountll(blocks);
@@ -1349,7 +979,7 @@ __global__ __launch_bounds__(64) void k_unlz4_sizes(const uint8_t* __restrict__ 
   if (bi >= nb) return;
   const UnBlock B = blk[bi];
   WalkEnd W;
-  const uint64_t size = unlz4_walk_vec(f, n, B, lane, seq_base(seqAll, B, bi), seq_cap(B), W);
+  const uint64_t size = unlz4_walk<Walk::kBlock>(f, n, B, lane, 0u, B.len, seq_base(seqAll, B, bi), seq_cap(B), W);
   if (lane == 0) {
     blk[bi].size = size;
     blk[bi].nseq = W.ns;
@@ -1425,8 +1055,8 @@ __global__ __launch_bounds__(64) void k_unlz4_spec(const uint8_t* __restrict__ f
   const uint32_t s0 = U.k * kUnSub, s1 = min(s0 + kUnSub, B.len);
   WalkEnd W{s0, 0u, 0u, 0u};
   const uint64_t sz = B.stored ? 0ull
-                               : unlz4_walk_v<true, false>(f, n, B, lane, s0, s1, sub_spec(seq, g), kUnSubCap, mask, s0,
-                                                           W, sub_cum(aux, g));
+                               : unlz4_walk<Walk::kSpec>(f, n, B, lane, s0, s1, sub_spec(seq, g), kUnSubCap, W, mask, s0,
+                                                         sub_cum(aux, g));
   __syncthreads();
   // the mask (4 words per lane) and its exclusive prefix bit counts per word
   static_assert(kSubWords == 256, "four mask words per lane");
@@ -1436,7 +1066,7 @@ __global__ __launch_bounds__(64) void k_unlz4_spec(const uint8_t* __restrict__ f
     m[k] = mask[4 * lane + k];
     c += __popc(m[k]);
   }
-  uint32_t pre = un_incl_scan_add(c, lane) - c;
+  uint32_t pre = wave_incl_scan_add(c) - c;
   uint32_t* gm = sub_mask(aux, g);
   uint16_t* gp = sub_mpre(aux, g);
 #pragma unroll
@@ -1481,7 +1111,7 @@ __device__ Join un_join(const uint8_t* __restrict__ f, uint64_t n, const UnBlock
   bool merged = (mask[(t - a0) >> 5] >> ((t - a0) & 31)) & 1u;
   if (!merged) {
     WalkEnd W;
-    const uint64_t sz = unlz4_walk_v<false, true>(f, n, B, lane, t, a1, sub_pre(seq, g), kUnSubCap, mask, a0, W);
+    const uint64_t sz = unlz4_walk<Walk::kJoin>(f, n, B, lane, t, a1, sub_pre(seq, g), kUnSubCap, W, mask, a0);
     if (sz == kNone) {
       J.ok = false;
     } else {
@@ -1599,11 +1229,11 @@ __global__ __launch_bounds__(64) void k_unlz4_fix(const uint8_t* __restrict__ f,
     }
     if (nOk) {
       const bool mine = lane < nOk;
-      const uint32_t incl = un_incl_scan_add(mine ? outLen : 0u, lane);
+      const uint32_t incl = wave_incl_scan_add(mine ? outLen : 0u);
       if (mine) subs[g].outRel = outRel + incl - outLen;
-      outRel += un_rdlane(incl, nOk - 1u);
-      t = un_rdlane(exit, nOk - 1u);
-      ended = (un_rdlane(flags, nOk - 1u) & 4u) != 0;
+      outRel += rdlane(incl, nOk - 1u);
+      t = rdlane(exit, nOk - 1u);
+      ended = (rdlane(flags, nOk - 1u) & 4u) != 0;
       k += nOk;
       if (nOk == 64u) continue;
     }
@@ -1680,11 +1310,11 @@ __global__ __launch_bounds__(64) void k_unlz4_sub(const uint8_t* __restrict__ f,
       const uint32_t cnt = to[li] - b0 < 64u ? to[li] - b0 : 64u;
       const uint4 q = lane < cnt ? seq[b0 + lane] : make_uint4(0u, 0u, 0u, 0u);
       const uint32_t tot = q.x + q.y;
-      const uint32_t incl = un_incl_scan_add(tot, lane);
+      const uint32_t incl = wave_incl_scan_add(tot);
       const uint32_t rel = incl - tot;  // output offset of the literals from P
       for (uint32_t j = 0; j < cnt; j++) {
-        const uint32_t L = un_rdlane(q.x, j), M = un_rdlane(q.y, j), off = un_rdlane(q.z, j), fr = un_rdlane(q.w, j);
-        const uint64_t Pj = P + un_rdlane(rel, j);
+        const uint32_t L = rdlane(q.x, j), M = rdlane(q.y, j), off = rdlane(q.z, j), fr = rdlane(q.w, j);
+        const uint64_t Pj = P + rdlane(rel, j);
         for (uint64_t k = lane; k < L; k += 64) {
           const uint32_t v = f[B.src + fr + k];
           img[Pj + k] = v;
@@ -1716,7 +1346,7 @@ __global__ __launch_bounds__(64) void k_unlz4_sub(const uint8_t* __restrict__ f,
           }
         }
       }
-      P += un_rdlane(incl, cnt - 1u);
+      P += rdlane(incl, cnt - 1u);
     }
   }
 }

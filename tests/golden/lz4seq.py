@@ -197,10 +197,12 @@ def layout(block):
 
 
 def _walk_windows(rows, src, length):
-    """The 256-byte register windows the whole-block header walk (unlz4_walk_vec) fills over a block whose
-    payload starts at frame offset `src`: yields (token window offset, header's last window offset) for every
-    token of the chain lying in the window that is current when the walk reaches it, and for the tokens
-    beyond the refill edge (window offsets 192..255) of that same window."""
+    """The 256-byte register windows the whole-block header walk (unlz4_walk<Walk::kBlock>) fills over a block
+    whose payload starts at frame offset `src`: yields (token window offset, header's last window offset) for
+    every token of the chain lying in the window that is current when the walk reaches it, and for the tokens
+    beyond the refill edge (window offsets 192..255) of that same window.  The speculative mode
+    (Walk::kSpec) of the same function walks the same windows over sub-segment 0 of a split block, which
+    starts at the block's first token: every family also runs through the `split` fixture."""
     seen = set()
     fast_end = length - 20 if length > 20 else 0
     toks = [r[0] for r in rows]
