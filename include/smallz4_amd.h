@@ -217,6 +217,9 @@ void sz4_set_timing(sz4_ctx* ctx, int on);
  * are the parse's choices (1 = literal).  Used by the intermediate parity tests. */
 void sz4_debug_stop_after(sz4_ctx* ctx, int stop_after);
 int sz4_debug_matches(sz4_ctx* ctx, uint32_t* len, uint16_t* dist, uint64_t n);
+/* The same copy, but always of the match arrays themselves: at levels > 3 what the parse was given
+ * (at levels 4..6 after the greedy/lazy skip bookkeeping), whatever stage the run stopped after. */
+int sz4_debug_parse_input(sz4_ctx* ctx, uint32_t* len, uint16_t* dist, uint64_t n);
 
 /* ---- decoder: the reference's smallz4cat ------------------------------------------------------
  * Decompress an LZ4 frame with the semantics of the reference decoder

@@ -479,11 +479,14 @@ class Compressor:
     def debug_stop_after(self, stage: int):
         self._lib.sz4_debug_stop_after(self._h, int(stage))
 
-    def debug_matches(self, n: int):
+    def debug_matches(self, n: int, parse_input: bool = False):
+        """Per-position (length, distance) of the last call (sz4_debug_matches); parse_input=True: always
+        the match arrays the parse was given, never its choices (sz4_debug_parse_input)."""
         import numpy as np
         ln = np.zeros(n, dtype=np.uint32)
         ds = np.zeros(n, dtype=np.uint16)
-        self._check(self._lib.sz4_debug_matches(self._h, ln.ctypes.data, ds.ctypes.data, n), "sz4_debug_matches")
+        name = "sz4_debug_parse_input" if parse_input else "sz4_debug_matches"
+        self._check(getattr(self._lib, name)(self._h, ln.ctypes.data, ds.ctypes.data, n), name)
         return ln, ds
 
     def device_bytes(self) -> int:

@@ -1717,16 +1717,26 @@ void sz4_debug_stop_after(sz4_ctx* c, int stop_after)
   if (c) c->stopAfter = stop_after;
 }
 
-int sz4_debug_matches(sz4_ctx* c, uint32_t* len, uint16_t* dist, uint64_t n)
+static int debug_copy(sz4_ctx* c, bool choices, uint32_t* len, uint16_t* dist, uint64_t n)
 {
   if (!c || !len || !dist) return SZ4_E_ARG;
   if (n * 4 > c->mlen.cap || n * 2 > c->mdist.cap) return SZ4_E_ARG;
-  // after the parse at optimal levels the lengths are the parse's choices
-  const uint32_t* lens = c->stopAfter == 4 && c->lastChain > (uint32_t)kGreedyMax ? c->sel() : c->mlen.as<uint32_t>();
+  const uint32_t* lens = choices ? c->sel() : c->mlen.as<uint32_t>();
   if (hipMemcpy(len, lens, n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(dist, c->mdist.p, n * 2, hipMemcpyDeviceToHost) != hipSuccess)
     return SZ4_E_DEVICE;
   return SZ4_OK;
+}
+
+int sz4_debug_matches(sz4_ctx* c, uint32_t* len, uint16_t* dist, uint64_t n)
+{
+  // after the parse at optimal levels the lengths are the parse's choices
+  return debug_copy(c, c && c->stopAfter == 4 && c->lastChain > (uint32_t)kGreedyMax, len, dist, n);
+}
+
+int sz4_debug_parse_input(sz4_ctx* c, uint32_t* len, uint16_t* dist, uint64_t n)
+{
+  return debug_copy(c, false, len, dist, n);
 }
 
 int sz4_unlz4_device(sz4_ctx* c, const void* d_frame, uint64_t frame_len, const void* d_dict, uint64_t dict_len,
