@@ -160,6 +160,57 @@ int sz4_unlz4_batch_typed_device(sz4_ctx* ctx, const void* d_blocks, const uint6
  * sz4_set_timing on; 0 when every width was 1). */
 float sz4_last_merge_ms(sz4_ctx* ctx);
 
+/* ---- decode queue: the batch decoders as an enqueue, nothing on the host ---------------------------------
+ * sz4_unlz4_batch_device takes host tables, waits for the stream twice and fails as a whole on one bad item.
+ * A decode queue takes DEVICE tables, writes per-item sizes and statuses on the device and only launches:
+ * sz4_dq_enqueue never synchronises, never allocates and never copies between host and device, and issues one
+ * chain of kernels on `stream` (no fork), so it can be captured in a HIP graph and replayed.
+ *
+ * sz4_dq_create reserves once what an enqueue of up to max_items items (1 .. 65536; else SZ4_E_ARG) holding up
+ * to max_src_bytes of blocks needs: a record per item and the sequence lists (about 5.4 bytes per source byte).
+ * The scratch belongs to the context: sz4_device_bytes counts it and sz4_set_device_limit bounds it (over the
+ * bound: SZ4_E_NOMEM), but neither a call that sheds buffers under the bound nor sz4_trim releases it while
+ * the queue lives -- a captured graph holds its addresses.  Destroy a queue before its context, and only after
+ * the last graph captured from it is gone and its last enqueue has finished.
+ * A queue serves one stream at a time: enqueues on one stream are ordered by the stream; using a queue from
+ * two streams needs the caller's own event between them.  An enqueue does not count as a call on the context
+ * (sz4_last_error is not touched); other calls on the context may run between enqueues. */
+typedef struct sz4_dq sz4_dq;
+
+/* per-item status, written to d_status */
+#define SZ4_ITEM_OK        0
+#define SZ4_ITEM_CORRUPT   1  /* what sz4_unlz4_batch_device answers SZ4_E_CORRUPT for */
+#define SZ4_ITEM_CAPACITY  2  /* decoded size > dst cap; d_out_sizes holds the size needed */
+#define SZ4_ITEM_ARG       3  /* width not 1/2/4/8, or a null pointer with a non-zero size/cap needed */
+#define SZ4_ITEM_QUEUE     4  /* the batch's source bytes exceed the queue's max_src_bytes at this item */
+#define SZ4_ITEM_INTERNAL  5  /* second pass decoded a different length than the size pass */
+
+int sz4_dq_create(sz4_ctx* ctx, uint32_t max_items, uint64_t max_src_bytes, sz4_dq** q);
+void sz4_dq_destroy(sz4_dq* q);
+
+/* Every d_ array is DEVICE memory of `count` entries, read (and written) when the kernels run, not when the
+ * call is made: a captured enqueue replayed after the caller rewrote the tables decodes the new tables.
+ *   d_src, d_src_sizes  item i is the bare block [d_src[i], d_src[i] + d_src_sizes[i]): size word + payload,
+ *                       exactly an item of sz4_unlz4_batch_device.  Any alignment, separate allocations;
+ *                       nothing is read outside the aligned 16-byte words that overlap an item
+ *   d_dst, d_dst_caps   it decodes to [d_dst[i], d_dst[i] + d_out_sizes[i]), any alignment; no store lands at or
+ *                       beyond d_dst[i] + d_dst_caps[i], nor beyond d_dst[i] + the decoded size
+ *   d_elems             element width per item (1, 2, 4 or 8), or NULL: every width 1.  For a width E > 1 the
+ *                       result is the merge of the decoded planes, what sz4_unlz4_batch_typed_device gives --
+ *                       the decoder stores every byte at its merged place, there is no second pass
+ *   d_out_sizes         decoded bytes per item (0 for a failed item, the size needed for SZ4_ITEM_CAPACITY)
+ *   d_status            SZ4_ITEM_* per item
+ * The decoded bytes are those of sz4_unlz4_batch_device / _typed_device for that item (zero history, items
+ * never see each other).  A size-0 item gives size 0 and SZ4_ITEM_OK, and neither of its pointers is looked
+ * at.  An item whose status is not SZ4_ITEM_OK has no byte of its destination written; the other items decode
+ * normally.  Items whose running source bytes pass max_src_bytes, from the first such item on, get
+ * SZ4_ITEM_QUEUE.  One wavefront decodes one item.
+ * Returns SZ4_OK once enqueued; SZ4_E_ARG before any device work for a null queue or table (d_elems may be
+ * NULL) or count > max_items; SZ4_E_DEVICE for a launch error. */
+int sz4_dq_enqueue(sz4_dq* q, const void* const* d_src, const uint32_t* d_src_sizes, void* const* d_dst,
+                   const uint32_t* d_dst_caps, const uint8_t* d_elems, uint32_t count, uint32_t* d_out_sizes,
+                   uint32_t* d_status, void* stream);
+
 /* Whole-stream compression with the exact semantics of
  * smallz4::lz4(getBytes, sendBytes, maxChainLength, dictionary, useLegacyFormat)
  * (reference smallz4.h:47-64): 4 MiB dependent blocks (8 MiB independent

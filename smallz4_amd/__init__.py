@@ -15,6 +15,8 @@ plus the data-parallel entry point the GPU is built for:
     Compressor().compress_batch_typed(items, elem_sizes) / unlz4_batch_typed(blocks, elem_sizes)
     Compressor().compress_tensor(t) / decompress_tensor(ct)
         -> the same for items of fixed-width elements, split into byte planes (planes.py) on the way
+    Compressor().decode_queue(max_items, max_src_bytes) -> DecodeQueue.enqueue(...) / tensor_tables(ct, out)
+        -> the batch decoders as an enqueue over device tables: no host synchronisation, graph-capturable
 
 All compression runs in the HIP library smallz4_amd/lib/libsmallz4_amd.so; there
 is no CPU fallback.
@@ -60,6 +62,106 @@ class CompressedTensor:
     @property
     def nbytes(self) -> int:
         return int(self.offsets[-1])
+
+
+@dataclasses.dataclass
+class DecodeTables:
+    """The device tables of one enqueue (DecodeQueue.tensor_tables builds them for a CompressedTensor)."""
+    src_ptrs: object     # int64: where every block starts
+    src_sizes: object    # int32: its bytes, size word included
+    dst_ptrs: object     # int64: where it decodes to
+    dst_caps: object     # int32: the room there
+    elems: object        # uint8: element width per item (or None: every width 1)
+    out_sizes: object    # int32, written by the enqueue: decoded bytes per item
+    status: object       # int32, written by the enqueue: SZ4_ITEM_* per item
+    count: int
+    keep: tuple = ()     # the tensors the pointers point into
+
+
+class DecodeQueue:
+    """An enqueue-only batch decoder (sz4_dq_*): device tables in, per-item sizes and statuses out on the
+    device, no host synchronisation -- an enqueue can be captured in a graph (torch.cuda.graph) and replayed
+    after the tables were rewritten.  Holds its scratch until close(); close it before its Compressor, and
+    after every graph captured from it is gone."""
+
+    def __init__(self, comp: "Compressor", max_items: int, max_src_bytes: int):
+        self._comp = comp
+        self._lib = comp._lib
+        self.device = comp.device
+        self.max_items, self.max_src_bytes = int(max_items), int(max_src_bytes)
+        h = ctypes.c_void_p()
+        comp._check(self._lib.sz4_dq_create(comp._h, self.max_items, self.max_src_bytes, ctypes.byref(h)), "sz4_dq_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if self._comp._h:  # a closed Compressor has released the scratch already
+                self._lib.sz4_dq_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _table(t, dtype, count, name):
+        # shape and type only: nothing here reads a tensor's contents
+        if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.numel() < count:
+            raise TypeError(f"{name} must be a contiguous device tensor of {dtype} with at least {count} entries")
+        return ctypes.c_void_p(t.data_ptr())
+
+    def enqueue(self, src_ptrs, src_sizes, dst_ptrs, dst_caps, out_sizes, status, elems=None, count=None, stream=None):
+        """Item i, the bare block of src_sizes[i] bytes at address src_ptrs[i], decodes to address dst_ptrs[i]
+        (room dst_caps[i]) as an item of width elems[i]; out_sizes[i] and status[i] (SZ4_ITEM_*) receive the
+        result when the stream gets there (see sz4_dq_enqueue).  Device tensors: int64 pointers, int32 sizes,
+        capacities, results and statuses, uint8 widths.  stream: a raw HIP stream (default: torch's current one)."""
+        import torch
+        if count is None:
+            count = src_ptrs.numel()
+        count = int(count)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.sz4_dq_enqueue(
+            self._h, self._table(src_ptrs, torch.int64, count, "src_ptrs"), self._table(src_sizes, torch.int32, count, "src_sizes"),
+            self._table(dst_ptrs, torch.int64, count, "dst_ptrs"), self._table(dst_caps, torch.int32, count, "dst_caps"),
+            None if elems is None else self._table(elems, torch.uint8, count, "elems"), count,
+            self._table(out_sizes, torch.int32, count, "out_sizes"), self._table(status, torch.int32, count, "status"),
+            ctypes.c_void_p(stream))
+        if rc != _native.SZ4_OK:
+            raise _native.NativeError(f"sz4_dq_enqueue failed ({rc})")
+
+    def enqueue_tables(self, t: DecodeTables, stream=None):
+        self.enqueue(t.src_ptrs, t.src_sizes, t.dst_ptrs, t.dst_caps, t.out_sizes, t.status, t.elems, t.count, stream)
+
+    def tensor_tables(self, ct: "CompressedTensor", out) -> DecodeTables:
+        """The tables that decode `ct` into the preallocated tensor `out` (ct's dtype and shape, contiguous, on
+        the device), built once: chunk pointers cut from ct.blocks and from out, every width the dtype's.
+        Enqueue them, or replay a captured enqueue, any number of times."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if out.dtype != ct.dtype or tuple(out.shape) != tuple(ct.shape) or not out.is_contiguous() or out.device != dev:
+            raise TypeError("out must be a contiguous device tensor of the compressed tensor's dtype and shape")
+        if not ct.blocks.is_cuda or ct.blocks.device != dev:
+            raise TypeError("ct.blocks must be on the queue's device")
+        e = out.element_size()
+        n = out.numel() * e
+        count = len(ct.offsets) - 1
+        if count != (n + ct.chunk_bytes - 1) // ct.chunk_bytes:
+            raise ValueError("the compressed tensor's chunks do not cover its shape")
+        caps = [min(ct.chunk_bytes, n - k * ct.chunk_bytes) for k in range(count)]
+        src, dst = ct.blocks.data_ptr(), out.data_ptr()
+
+        def table(values, dtype):
+            return torch.tensor(values, dtype=dtype).to(dev) if values else torch.empty(0, dtype=dtype, device=dev)
+
+        return DecodeTables(
+            table([src + int(ct.offsets[k]) for k in range(count)], torch.int64),
+            table([int(ct.offsets[k + 1]) - int(ct.offsets[k]) for k in range(count)], torch.int32),
+            table([dst + k * ct.chunk_bytes for k in range(count)], torch.int64), table(caps, torch.int32),
+            table([e] * count, torch.uint8), torch.zeros(count, dtype=torch.int32, device=dev),
+            torch.zeros(count, dtype=torch.int32, device=dev), count, (ct.blocks, out))
 
 
 class Compressor:
@@ -414,6 +516,11 @@ class Compressor:
         if off[-1] != n:
             raise _native.NativeError(f"the blocks decode to {off[-1]} bytes, the tensor has {n}")
         return out.view(ct.dtype).reshape(ct.shape)
+
+    def decode_queue(self, max_items: int, max_src_bytes: int) -> "DecodeQueue":
+        """An enqueue-only batch decoder for up to max_items items of max_src_bytes of blocks in all per
+        enqueue (sz4_dq_create); its scratch counts as this context's until the queue is closed."""
+        return DecodeQueue(self, max_items, max_src_bytes)
 
     def last_merge_ms(self) -> float:
         """Device time of the last unlz4_batch_typed_device call's merge kernel (with set_timing on)."""

@@ -16,6 +16,15 @@ SZ4_OK = 0
 SZ4_E_ARG = -1
 SZ4_E_CAPACITY = -3
 SZ4_E_CORRUPT = -6
+SZ4_E_DEVICE = -2
+SZ4_E_NOMEM = -4
+# per-item statuses of the decode queue (sz4_dq_enqueue)
+SZ4_ITEM_OK = 0
+SZ4_ITEM_CORRUPT = 1
+SZ4_ITEM_CAPACITY = 2
+SZ4_ITEM_ARG = 3
+SZ4_ITEM_QUEUE = 4
+SZ4_ITEM_INTERNAL = 5
 SZ4_HEADER_SMALLZ4 = 0
 SZ4_HEADER_INDEPENDENT = 1
 SZ4_HEADER_NONE = 2
@@ -47,6 +56,10 @@ SIGNATURES = {
     "sz4_unlz4_batch_typed_device": (_i32, [_vp, _vp, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_uint8), _u64, _vp,
                                             _u64, ctypes.POINTER(_u64), _vp]),
     "sz4_last_merge_ms": (ctypes.c_float, [_vp]),
+    # decode queue: every table is a device pointer
+    "sz4_dq_create": (_i32, [_vp, _u32, _u64, ctypes.POINTER(_vp)]),
+    "sz4_dq_destroy": (None, [_vp]),
+    "sz4_dq_enqueue": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     "sz4_lz4": (_i32, [_vp, _vp, _u64, _u32, _vp, _u64, _i32, _vp, _u64, ctypes.POINTER(_u64)]),
     "sz4_lz4_bound": (_u64, [_u64, _i32]),
     "sz4_lz4_stream": (_i32, [_vp, GET_BYTES, SEND_BYTES, _u32, _vp, _u64, _i32, _vp]),

@@ -966,8 +966,6 @@ uint64_t legacy_block_length(const uint8_t* p, uint64_t len)
   return w;
 }
 
-constexpr uint32_t kMaxFrameBlock = (uint32_t)(kBlockMaxLegacy + kBlockMaxLegacy / 255 + 16);  // LZ4 compress bound
-
 int stream_decompress(sz4_ctx* c, sz4_get_byte get, sz4_send_out send, const uint8_t* dict, uint64_t dictLen, void* user)
 {
   uint32_t sig = 0;
@@ -1315,7 +1313,8 @@ void sz4_trim(sz4_ctx* c)
   DeviceGuard guard(c->device);
   for (hipStream_t x : {c->stream, c->upStream, c->downStream})
     if (x) hipStreamSynchronize(x);
-  for (DevBuf* b : c->budget.bufs) b->release();
+  for (DevBuf* b : c->budget.bufs)
+    if (!b->held) b->release();  // a live decode queue keeps its scratch
   for (HostBuf* b : {&c->hostIn[0], &c->hostIn[1], &c->hostOut[0], &c->hostOut[1]}) b->release();
   c->uploadedVersion = ~0ull;
 }
@@ -1657,6 +1656,68 @@ int sz4_unlz4_batch_typed_device(sz4_ctx* c, const void* d_blocks, const uint64_
 {
   if (count && !elem_sizes) return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
   return unlz4_batch(c, d_blocks, offsets, elem_sizes, count, d_out, out_cap, out_offsets, stream);
+}
+
+// ---- decode queue: everything an enqueue needs, reserved once on the context's budget and held -----------
+static_assert(SZ4_ITEM_OK == kItemOk && SZ4_ITEM_CORRUPT == kItemCorrupt && SZ4_ITEM_CAPACITY == kItemCapacity &&
+                  SZ4_ITEM_ARG == kItemArg && SZ4_ITEM_QUEUE == kItemQueue && SZ4_ITEM_INTERNAL == kItemInternal,
+              "the kernels' item statuses are the header's");
+
+struct sz4_dq {
+  sz4_ctx* ctx;
+  uint32_t maxItems;
+  uint64_t maxSrc;
+  DevBuf blk, seqOff, seq;  // UnBlock and list offset per item; the sequence lists
+  sz4_dq(sz4_ctx* c, uint32_t items, uint64_t src)
+      : ctx(c), maxItems(items), maxSrc(src), blk(c->budget, true), seqOff(c->budget, true), seq(c->budget, true) {}
+  void detach()
+  {
+    for (DevBuf* b : {&blk, &seqOff, &seq}) b->detach();
+  }
+};
+
+int sz4_dq_create(sz4_ctx* c, uint32_t max_items, uint64_t max_src_bytes, sz4_dq** q)
+{
+  if (q) *q = nullptr;
+  if (!c || !q) return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
+  if (max_items < 1 || max_items > 65536) return c->fail(SZ4_E_ARG, "max_items is not 1 .. 65536");
+  c->begin_call();
+  DeviceGuard guard(c->device);
+  sz4_dq* d = new (std::nothrow) sz4_dq(c, max_items, max_src_bytes);
+  if (!d) return c->fail(SZ4_E_NOMEM, "host allocation");
+  hipError_t e;
+  if ((e = d->blk.reserve((uint64_t)max_items * sizeof(UnBlock))) || (e = d->seqOff.reserve((uint64_t)max_items * 8)) ||
+      (e = d->seq.reserve(unlz4_seq_entries(max_src_bytes, max_items) * sizeof(uint4)))) {
+    d->detach();
+    delete d;
+    return c->fail(SZ4_E_NOMEM, "decode queue scratch", e);
+  }
+  *q = d;
+  return SZ4_OK;
+}
+
+void sz4_dq_destroy(sz4_dq* q)
+{
+  if (!q) return;
+  DeviceGuard guard(q->ctx->device);
+  q->detach();
+  delete q;
+}
+
+// Launches only: no allocation, no copy, no wait, and nothing of the context's call state is touched
+int sz4_dq_enqueue(sz4_dq* q, const void* const* d_src, const uint32_t* d_src_sizes, void* const* d_dst,
+                   const uint32_t* d_dst_caps, const uint8_t* d_elems, uint32_t count, uint32_t* d_out_sizes,
+                   uint32_t* d_status, void* stream)
+{
+  if (!q || !d_src || !d_src_sizes || !d_dst || !d_dst_caps || !d_out_sizes || !d_status || count > q->maxItems)
+    return SZ4_E_ARG;
+  if (!count) return SZ4_OK;
+  DeviceGuard guard(q->ctx->device);
+  const DqTables T{reinterpret_cast<const uint64_t*>(d_src), d_src_sizes, reinterpret_cast<const uint64_t*>(d_dst),
+                   d_dst_caps, d_elems, d_out_sizes, d_status};
+  launch_unlz4_dq(T, count, q->maxSrc, q->blk.as<UnBlock>(), q->seqOff.as<uint64_t>(), q->seq.as<uint4>(),
+                  (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? SZ4_OK : SZ4_E_DEVICE;
 }
 
 int sz4_lz4_stream(sz4_ctx* c, sz4_get_bytes get_bytes, sz4_send_bytes send_bytes, uint32_t max_chain, const void* dict,

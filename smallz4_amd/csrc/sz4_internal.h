@@ -211,15 +211,15 @@ void launch_emit(const PipeArgs& a, hipStream_t s);
 
 // decoder (sz4_unlz4.hip): one block of an LZ4 frame
 struct UnBlock {
-  uint64_t src;       // payload offset in the frame
-  uint64_t dst;       // output offset (set by the host after the sizes pass)
+  uint64_t src;       // payload offset in the frame (decode queue: its address, the frame base being null)
+  uint64_t dst;       // output offset (set by the host after the sizes pass; decode queue: the address)
   uint64_t size;      // decoded bytes (k_unlz4_sizes / k_unlz4_fix), kNone when malformed
   uint32_t len;       // payload bytes
   uint32_t stored;    // 1: uncompressed block
   uint32_t nseq;      // sequences recorded by k_unlz4_sizes
   uint32_t subFirst;  // split mode: first sub-segment of the block
   uint32_t subCount;  // split mode: its sub-segments (ceil(len / kUnSub))
-  uint32_t pad;
+  uint32_t pad;       // decode queue: the item's element width (read by the kTyped decoders alone)
 };
 // Split mode (frames with large blocks): every block is cut into sub-segments of kUnSub payload bytes,
 // parsed speculatively from their first byte (k_unlz4_spec), joined to the true token chain per block
@@ -269,6 +269,25 @@ void launch_unlz4_blocks_indep(const uint8_t* f, uint64_t n, const UnBlock* blk,
 // least 4 bytes); fills src / len / stored and sets *status when a size word disagrees with its extent
 void launch_unlz4_batch_plan(const uint8_t* f, const uint64_t* ext, uint32_t nb, UnBlock* blk, uint32_t* status,
                              hipStream_t s);
+// decode queue (sz4_dq_enqueue): the caller's device tables, `count` entries each, read and written by the
+// kernels alone.  Item i is the bare block [src[i], src[i] + srcSizes[i]) and decodes to dst[i] (capacity
+// dstCaps[i]) as an item of width elems[i] (null: 1); outSizes and status (kItem*, SZ4_ITEM_*) are the result
+constexpr uint32_t kMaxFrameBlock = (uint32_t)(kBlockMaxLegacy + kBlockMaxLegacy / 255 + 16);  // LZ4 compress bound
+constexpr uint32_t kItemOk = 0, kItemCorrupt = 1, kItemCapacity = 2, kItemArg = 3, kItemQueue = 4, kItemInternal = 5;
+struct DqTables {
+  const uint64_t* src;
+  const uint32_t* srcSizes;
+  const uint64_t* dst;
+  const uint32_t* dstCaps;
+  const uint8_t* elems;
+  uint32_t* outSizes;
+  uint32_t* status;
+};
+// plan (one workgroup: checks, running source bytes against maxSrc, the scan of the sequence-list needs into
+// seqOff), size pass and decode pass, one wavefront per item: three kernels in a row on s, nothing else.
+// blk, seqOff: count entries; seq: unlz4_seq_entries(maxSrc, count) entries.  count > 0
+void launch_unlz4_dq(const DqTables& T, uint32_t count, uint64_t maxSrc, UnBlock* blk, uint64_t* seqOff, uint4* seq,
+                     hipStream_t s);
 // split mode: seq holds 2 * kUnSubCap entries per sub-segment (re-parsed prefix, speculative list), masks
 // kUnAuxWords words per sub-segment (the token-start mask and k_unlz4_spec's side tables)
 void launch_unlz4_split_sizes(const uint8_t* f, uint64_t n, UnBlock* blk, uint32_t nb, UnSub* subs, uint32_t nsub,

@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <vector>
 
 namespace sz4 {
@@ -33,7 +34,16 @@ struct DevBuf {
   size_t cap = 0;
   Budget& bud;
   uint64_t lastGen = 0;
-  explicit DevBuf(Budget& b) : bud(b) { b.bufs.push_back(this); }
+  // held: a buffer whose address something outside the context's calls keeps (a decode queue's scratch, which
+  // a captured graph names): counted and bounded like any other, but neither shed() nor sz4_trim releases it
+  bool held = false;
+  explicit DevBuf(Budget& b, bool keep = false) : bud(b), held(keep) { b.bufs.push_back(this); }
+  // a buffer that ends before its budget's owner does leaves the list (decode queues; the context's own never do)
+  void detach()
+  {
+    release();
+    bud.bufs.erase(std::remove(bud.bufs.begin(), bud.bufs.end(), this), bud.bufs.end());
+  }
   DevBuf(const DevBuf&) = delete;  // neither copied nor moved
   DevBuf& operator=(const DevBuf&) = delete;
   hipError_t reserve(size_t bytes)
@@ -78,7 +88,7 @@ inline uint64_t Budget::shed()
 {
   uint64_t freed = 0;
   for (DevBuf* b : bufs)
-    if (b->p && b->lastGen != gen) {
+    if (b->p && b->lastGen != gen && !b->held) {
       freed += b->cap;
       b->release();
       shedCount++;

@@ -28,6 +28,9 @@
 //                   checks the assumptions per block (re-joining the wrong ones), k_unlz4_sub decodes every
 //                   sub-segment into a value-or-reference image, k_unlz4_pack resolves the references
 //
+//   decode queue (sz4_dq_enqueue): k_unlz4_dq_plan -> k_unlz4_dq_sizes -> k_unlz4_dq_blocks, the batch decoder
+//                   over device tables of pointers with per-item statuses; typed items stored merged (typed_map)
+//
 //   One header walker, unlz4_walk<Walk>, parses tokens for all of them: Walk::kBlock in k_unlz4_sizes,
 //   Walk::kSpec in k_unlz4_spec, Walk::kJoin in un_join (k_unlz4_join, k_unlz4_fix).  The wave helpers
 //   (readlane, DPP scans and row sums, wave_path) are the shared ones of sz4_device.h.
@@ -42,6 +45,7 @@
 
 #include "sz4_device.h"
 #include "sz4_internal.h"
+#include "sz4_typed_map.h"
 
 namespace sz4 {
 #ifndef SZ4_DIAG
@@ -350,16 +354,26 @@ __device__ uint64_t unlz4_walk(const uint8_t* __restrict__ f, uint64_t n, const 
 // kIndep (the batch decoder's bare blocks): the block decodes on its own.  Nothing precedes it, so a match
 // source below B.dst reads 0 -- the reference's zero-initialised history -- and neither another block's
 // output nor its done flag is ever read (blk, done, dict are unused).
-template <bool kIndep>
+// kTyped (the decode queue's typed items, kIndep only): the block is the byte-plane split of an item of B.size
+// bytes and width B.pad, and every access to `out` -- the stores, the reads of drained output, the stored
+// block's copy -- goes to where the merge puts that position (typed_map); the ring stays indexed by position.
+template <bool kIndep, bool kTyped = false>
 __device__ uint64_t unlz4_decode(const uint8_t* __restrict__ f, uint64_t n, const UnBlock& B, uint32_t bi, uint32_t lane,
                                  const uint4* __restrict__ seq, uint8_t* __restrict__ out, uint8_t* __restrict__ ring,
                                  const uint8_t* __restrict__ dict, uint64_t dl, const UnBlock* __restrict__ blk,
                                  uint32_t* __restrict__ done, uint32_t* __restrict__ status, uint32_t b0Start = 0,
                                  uint64_t wStart = 0)
 {
+  static_assert(kIndep || !kTyped, "typed items are independent blocks");
+  const uint32_t tE = kTyped ? B.pad : 1u, tM = kTyped ? (uint32_t)B.size / tE : 0u;
+  // the address of output position a (both absolute: B.dst + block-relative)
+  auto at = [&](uint64_t a) -> uint64_t {
+    if constexpr (kTyped) return B.dst + typed_map<uint32_t>((uint32_t)(a - B.dst), tM, tE);
+    return a;
+  };
   if (B.stored) {
     // later blocks read it from `out`
-    for (uint64_t k = lane; k < B.len; k += 64) out[B.dst + k] = f[B.src + k];
+    for (uint64_t k = lane; k < B.len; k += 64) out[at(B.dst + k)] = f[B.src + k];
     return B.len;
   }
   uint64_t floorPos = B.dst;  // output below this is read only after its blocks are done
@@ -406,13 +420,13 @@ __device__ uint64_t unlz4_decode(const uint8_t* __restrict__ f, uint64_t n, cons
           const uint32_t c = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)w1);
           const uint8_t v = (uint8_t)(((rel & 4u) ? c : a) >> (8 * (rel & 3u)));
           if (lane < L) {
-            out[P + lane] = v;
+            out[at(P + lane)] = v;
             ring[(P + lane) & (kRing - 1u)] = v;
           }
         } else {
           for (uint64_t k = lane; k < L; k += 64) {
             const uint8_t v = f[B.src + fr + k];
-            out[P + k] = v;
+            out[at(P + k)] = v;
             ring[(P + k) & (kRing - 1u)] = v;
           }
         }
@@ -458,13 +472,13 @@ __device__ uint64_t unlz4_decode(const uint8_t* __restrict__ f, uint64_t n, cons
           uint8_t v = 0;
           if (jj < M) {
             if (s >= (int64_t)B.dst && s >= ringLo) v = ring[(uint64_t)s & (kRing - 1u)];
-            else if (kIndep) v = s >= (int64_t)B.dst ? out[s] : (uint8_t)0;  // drained output of this block, or 0
+            else if (kIndep) v = s >= (int64_t)B.dst ? out[at((uint64_t)s)] : (uint8_t)0;  // drained output of this block, or 0
             else if (s >= 0) v = out[s];  // drained output of this block, or an earlier (finished) block
             else if ((uint64_t)(-s) <= dl) v = dict[dl - (uint64_t)(-s)];  // the dictionary's tail
             // else 0: before the history (oz_unlz4's zero-initialised history)
           }
           if (jj < M) {
-            out[Q + jj] = v;
+            out[at(Q + jj)] = v;
             ring[(Q + jj) & (kRing - 1u)] = v;
           }
         }
@@ -484,16 +498,21 @@ __device__ uint64_t unlz4_decode(const uint8_t* __restrict__ f, uint64_t n, cons
 // byte, at most log2(64) rounds per distinct offset).  Blocks whose matches stay inside the block
 // (independent blocks: every frame bench.py decodes); the first batch with a match reaching below the
 // block start (linked blocks, a dictionary) or an empty sequence continues in unlz4_decode (kIndep: in its
-// independent mode).
-template <bool kIndep>
+// independent mode).  kTyped: as in unlz4_decode.
+template <bool kIndep, bool kTyped = false>
 __device__ uint64_t unlz4_decode_vec(const uint8_t* __restrict__ f, uint64_t n, const UnBlock& B, uint32_t bi,
                                      uint32_t lane, const uint4* __restrict__ seq, uint8_t* __restrict__ out,
                                      uint8_t* __restrict__ ring, uint32_t* __restrict__ slot,
                                      const uint8_t* __restrict__ dict, uint64_t dl, const UnBlock* __restrict__ blk,
                                      uint32_t* __restrict__ done, uint32_t* __restrict__ status)
 {
+  const uint32_t tE = kTyped ? B.pad : 1u, tM = kTyped ? (uint32_t)B.size / tE : 0u;
+  auto at = [&](uint64_t x) -> uint64_t {  // the address of block-relative output position x
+    if constexpr (kTyped) return B.dst + typed_map<uint32_t>((uint32_t)x, tM, tE);
+    return B.dst + x;
+  };
   if (B.stored) {
-    for (uint64_t k = lane; k < B.len; k += 64) out[B.dst + k] = f[B.src + k];
+    for (uint64_t k = lane; k < B.len; k += 64) out[at(k)] = f[B.src + k];
     return B.len;
   }
   uint64_t w = 0;            // block-relative output of the batches done
@@ -511,7 +530,7 @@ __device__ uint64_t unlz4_decode_vec(const uint8_t* __restrict__ f, uint64_t n, 
     if (__ballot(far || (lane < cnt && tot == 0u))) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      return unlz4_decode<kIndep>(f, n, B, bi, lane, seq, out, ring, dict, dl, blk, done, status, b0, w);
+      return unlz4_decode<kIndep, kTyped>(f, n, B, bi, lane, seq, out, ring, dict, dl, blk, done, status, b0, w);
     }
     uint32_t jc = 0;  // 1 + the sequence covering the byte before the window
     for (uint32_t W = 0; W < blen; W += 64) {
@@ -545,7 +564,7 @@ __device__ uint64_t unlz4_decode_vec(const uint8_t* __restrict__ f, uint64_t n, 
       uint32_t val = 0;
       if (valid && lit) val = f[B.src + fr + k];
       // the ring holds [cur - kRing, cur) until this window's stores; further back is drained in `out`
-      else if (valid && !inWin) val = src + kRing >= cur ? ring[(B.dst + src) & (kRing - 1u)] : out[B.dst + src];
+      else if (valid && !inWin) val = src + kRing >= cur ? ring[(B.dst + src) & (kRing - 1u)] : out[at(src)];
       bool known = !inWin;
       uint32_t ref = inWin ? (uint32_t)(src - cur) : lane;
       while (__ballot(!known)) {
@@ -562,7 +581,7 @@ __device__ uint64_t unlz4_decode_vec(const uint8_t* __restrict__ f, uint64_t n, 
         }
       }
       if (valid) {
-        out[B.dst + ob] = (uint8_t)val;
+        out[at(ob)] = (uint8_t)val;
         ring[(B.dst + ob) & (kRing - 1u)] = (uint8_t)val;
       }
     }
@@ -1498,6 +1517,144 @@ void launch_unlz4_batch_plan(const uint8_t* f, const uint64_t* ext, uint32_t nb,
                              hipStream_t s)
 {
   if (nb) hipLaunchKernelGGL(k_unlz4_batch_plan, dim3((nb + 255) / 256), dim3(256), 0, s, f, ext, nb, blk, status);
+}
+
+// ================================================================================================
+// Decode queue (sz4_dq_enqueue): the batch decoder over device tables of pointers, nothing on the host.
+// An item's UnBlock holds absolute addresses in src / dst and the kernels take null bases, so the walker
+// and the decoders address it as they address a frame.  Their read bound n is the item's own end, src +
+// len: nothing is read outside the aligned 16-byte words that overlap an item (the gather's rule) -- the
+// walker's window starts at the cursor rounded down to 4 and the literal window at 8, both at or above the
+// payload's first byte rounded down, and bytes at or past n read as 0 without a load.
+// ================================================================================================
+
+// inclusive wavefront sum of values below 2^32 without overflow: the 16-bit halves by the DPP scan
+__device__ __forceinline__ uint64_t wave_incl_scan_add64(uint32_t v)
+{
+  const uint32_t lo = wave_incl_scan_add(v & 0xFFFFu), hi = wave_incl_scan_add(v >> 16);
+  return ((uint64_t)hi << 16) + lo;
+}
+
+// One workgroup plans the whole batch from the tables alone (coalesced reads, no item byte is touched):
+// the running source bytes against the queue's bound, the checks that need no payload, every item's
+// UnBlock and the exclusive scan of the sequence-list needs (seq_cap), which gives item i its list at
+// seqAll + seqOff[i].  Every item's status and result size are written here (0 for what the size pass fills in).
+__global__ __launch_bounds__(1024) void k_unlz4_dq_plan(DqTables T, uint32_t count, uint64_t maxSrc, UnBlock* __restrict__ blk,
+                                                         uint64_t* __restrict__ seqOff)
+{
+  __shared__ uint64_t s_b[16], s_q[16];
+  __shared__ uint64_t s_cb, s_cq;  // the sums of the items before this round
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+  if (tid == 0) s_cb = s_cq = 0;
+  __syncthreads();
+  for (uint32_t b = 0; b < count; b += 1024) {
+    const uint32_t i = b + tid;
+    const bool in = i < count;
+    const uint32_t size = in ? T.srcSizes[i] : 0u;
+    const uint64_t xb = wave_incl_scan_add64(size);
+    if (lane == 63) s_b[wv] = xb;
+    __syncthreads();
+    uint64_t run = s_cb + xb;  // source bytes up to and including this item
+    for (uint32_t k = 0; k < wv; k++) run += s_b[k];
+    uint32_t st = kItemOk, need = 0, E = 1;
+    uint64_t src = 0, dst = 0;
+    if (in) {
+      src = T.src[i];
+      dst = T.dst[i];
+      E = T.elems ? T.elems[i] : 1u;
+      if (run > maxSrc) st = kItemQueue;
+      else if (size == 0) st = kItemOk;  // an empty item: neither pointer is looked at
+      else if ((E != 1 && E != 2 && E != 4 && E != 8) || src == 0) st = kItemArg;
+      else if (size < 4 || size - 4 > kMaxFrameBlock) st = kItemCorrupt;
+      else if (dst == 0 && T.dstCaps[i] != 0) st = kItemArg;
+      else need = (size - 4) / 3 + 2;
+    }
+    const uint64_t xq = wave_incl_scan_add64(need);
+    if (lane == 63) s_q[wv] = xq;
+    __syncthreads();
+    uint64_t lists = s_cq + xq;
+    for (uint32_t k = 0; k < wv; k++) lists += s_q[k];
+    if (in) {
+      UnBlock B{};
+      B.src = src + 4;
+      B.dst = dst;
+      B.len = need ? size - 4 : 0u;
+      B.stored = 1;  // until the size pass has read the size word
+      B.pad = E;     // the element width
+      blk[i] = B;
+      seqOff[i] = lists - need;
+      T.status[i] = st;
+      T.outSizes[i] = 0;
+    }
+    __syncthreads();
+    if (tid == 1023) {
+      s_cb = run;
+      s_cq = lists;
+    }
+    __syncthreads();
+  }
+}
+
+// one wavefront per item still OK: its size word against its extent, then k_unlz4_sizes' walk under the
+// item's own read bound; the decoded size against the capacity
+__global__ __launch_bounds__(64) void k_unlz4_dq_sizes(const uint8_t* __restrict__ f, DqTables T, uint32_t count,
+                                                       UnBlock* __restrict__ blk, const uint64_t* __restrict__ seqOff,
+                                                       uint4* __restrict__ seqAll)
+{
+  const uint32_t bi = blockIdx.x, lane = threadIdx.x;
+  if (bi >= count || T.status[bi] != kItemOk || T.srcSizes[bi] == 0) return;
+  UnBlock B = blk[bi];
+  const uint64_t at = B.src - 4;
+  const uint32_t word = (uint32_t)f[at] | ((uint32_t)f[at + 1] << 8) | ((uint32_t)f[at + 2] << 16) | ((uint32_t)f[at + 3] << 24);
+  uint64_t size = kNone;
+  WalkEnd W{};
+  if ((word & 0x7FFFFFFFu) == B.len) {
+    B.stored = (word >> 31) | (B.len == 0 ? 1u : 0u);
+    size = unlz4_walk<Walk::kBlock>(f, B.src + B.len, B, lane, 0u, B.len, seqAll + seqOff[bi], seq_cap(B), W);
+  }
+  if (lane != 0) return;
+  if (size == kNone) {
+    T.status[bi] = kItemCorrupt;
+  } else if (size > (uint64_t)T.dstCaps[bi]) {
+    T.status[bi] = kItemCapacity;
+    T.outSizes[bi] = size > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)size;
+  } else {
+    blk[bi].size = size;
+    blk[bi].stored = B.stored;
+    blk[bi].nseq = W.ns;
+    T.outSizes[bi] = (uint32_t)size;
+  }
+}
+
+// one wavefront per item still OK replays its list: k_unlz4_blocks<true>, a typed item through typed_map
+__global__ __launch_bounds__(64) void k_unlz4_dq_blocks(const uint8_t* __restrict__ f, uint8_t* __restrict__ out, DqTables T,
+                                                        uint32_t count, const UnBlock* __restrict__ blk,
+                                                        const uint64_t* __restrict__ seqOff, const uint4* __restrict__ seqAll)
+{
+  __shared__ uint8_t ring[kRing];
+  __shared__ uint32_t slot[64];
+  const uint32_t bi = blockIdx.x, lane = threadIdx.x;
+  if (bi >= count || T.status[bi] != kItemOk) return;
+  const UnBlock B = blk[bi];
+  if (B.size == 0) return;
+  const uint64_t n = B.src + B.len;
+  const uint4* seq = seqAll + seqOff[bi];
+  // an item shorter than one element is its own merge
+  const uint64_t got = B.pad > 1u && B.size >= (uint64_t)B.pad
+                           ? unlz4_decode_vec<true, true>(f, n, B, bi, lane, seq, out, ring, slot, nullptr, 0, blk, nullptr, nullptr)
+                           : unlz4_decode_vec<true, false>(f, n, B, bi, lane, seq, out, ring, slot, nullptr, 0, blk, nullptr, nullptr);
+  if (lane == 0 && got != B.size) T.status[bi] = kItemInternal;
+}
+
+void launch_unlz4_dq(const DqTables& T, uint32_t count, uint64_t maxSrc, UnBlock* blk, uint64_t* seqOff, uint4* seq,
+                     hipStream_t s)
+{
+  // the bases of the absolute addresses: null, and passed as arguments so that the kernels index them as any frame
+  const uint8_t* f = nullptr;
+  uint8_t* out = nullptr;
+  hipLaunchKernelGGL(k_unlz4_dq_plan, dim3(1), dim3(1024), 0, s, T, count, maxSrc, blk, seqOff);
+  hipLaunchKernelGGL(k_unlz4_dq_sizes, dim3(count), dim3(64), 0, s, f, T, count, blk, seqOff, seq);
+  hipLaunchKernelGGL(k_unlz4_dq_blocks, dim3(count), dim3(64), 0, s, f, out, T, count, blk, seqOff, seq);
 }
 
 }  // namespace sz4
