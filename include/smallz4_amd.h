@@ -183,7 +183,7 @@ typedef struct sz4_dq sz4_dq;
 #define SZ4_ITEM_CAPACITY  2  /* decoded size > dst cap; d_out_sizes holds the size needed */
 #define SZ4_ITEM_ARG       3  /* width not 1/2/4/8, or a null pointer with a non-zero size/cap needed */
 #define SZ4_ITEM_QUEUE     4  /* the batch's source bytes exceed the queue's max_src_bytes at this item */
-#define SZ4_ITEM_INTERNAL  5  /* second pass decoded a different length than the size pass */
+#define SZ4_ITEM_INTERNAL  5  /* second pass decoded a different length than the size pass (compress queue: below) */
 
 int sz4_dq_create(sz4_ctx* ctx, uint32_t max_items, uint64_t max_src_bytes, sz4_dq** q);
 void sz4_dq_destroy(sz4_dq* q);
@@ -210,6 +210,65 @@ void sz4_dq_destroy(sz4_dq* q);
 int sz4_dq_enqueue(sz4_dq* q, const void* const* d_src, const uint32_t* d_src_sizes, void* const* d_dst,
                    const uint32_t* d_dst_caps, const uint8_t* d_elems, uint32_t count, uint32_t* d_out_sizes,
                    uint32_t* d_status, void* stream);
+
+/* ---- compress queue: sz4_compress_batch_typed_device as an enqueue, nothing on the host --------------------
+ * The batch compressors plan, allocate, upload and wait on every call.  A compress queue fixes the item count,
+ * the item sizes and element widths and the level when it is created; the sources, the output and the result
+ * tables are device memory read and written when the kernels run.  sz4_cq_enqueue never synchronises, never
+ * allocates and never copies between host and device, and issues one chain of kernels on `stream`
+ * (no fork), so it can be captured in a HIP graph and replayed.  Its result tables are by construction the
+ * d_src / d_src_sizes of sz4_dq_enqueue: a compress -> decode round trip needs no host step in between.
+ *
+ * Limits, all checked by sz4_cq_create before any device work (SZ4_E_ARG, *q = NULL):
+ *   count       1 .. 32768 items
+ *   sizes       at most 4 MiB each (0: an empty item, which has no block); widths 1, 2, 4 or 8
+ *   max_chain   0 or 7 .. 65535.  Levels 1 .. 6 (greedy / lazy) settle their shortcut intervals in rounds
+ *               that read a status word on the host, and so does dictionary mode: neither is available here
+ *   staged      the sum of the sizes, each rounded up to 64, is at most 448 MiB
+ * One kind of item is advised: when an item does not fit the match finders' LDS (more than 65541 bytes) every
+ * item of the queue runs through the finders that read their window from HBM -- the bytes are the same, the
+ * small items are slower.  The synchronous calls split such a set into two runs; a queue does not.
+ *
+ * sz4_cq_create plans the run, reserves everything an enqueue names -- about 50 bytes per staged byte plus
+ * 16 KiB per item -- uploads the plan and waits once.  The scratch belongs to the context: sz4_device_bytes
+ * counts it and sz4_set_device_limit bounds it (over the bound: SZ4_E_NOMEM, nothing left allocated), but
+ * neither a call that sheds buffers under the bound nor sz4_trim releases it while the queue lives -- a captured
+ * graph holds its addresses.  It is the queue's own: other calls on the context, compressor calls included,
+ * may run between enqueues.  Destroy a queue before its context, and only after the last graph captured from it
+ * is gone and its last enqueue has finished.
+ * A queue serves one stream at a time: enqueues on one stream are ordered by the stream; using a queue from
+ * two streams needs the caller's own event between them.  An enqueue does not count as a call on the context
+ * (sz4_last_error is not touched); sz4_set_timing and sz4_debug_stop_after do not apply to it. */
+typedef struct sz4_cq sz4_cq;
+
+/* sizes[count], elem_sizes[count] (NULL: every width 1) are HOST arrays, copied. */
+int sz4_cq_create(sz4_ctx* ctx, const uint32_t* sizes, const uint8_t* elem_sizes, uint32_t count,
+                  uint32_t max_chain, sz4_cq** q);
+void sz4_cq_destroy(sz4_cq* q);
+/* == sz4_batch_bound(sizes, count); 0 for a null queue */
+uint64_t sz4_cq_bound(const sz4_cq* q);
+
+/*   d_src          DEVICE table of `count` device addresses, read when the kernels run: a captured enqueue
+ *                  replayed after the table was rewritten compresses the new buffers.  Any alignment; nothing
+ *                  is read outside the aligned 16-byte words that overlap an item.  The entry of an empty item
+ *                  is not looked at.  A null entry of a non-empty item is never dereferenced: the item is
+ *                  compressed as zeros and its status is SZ4_ITEM_ARG
+ *   d_out, out_cap the output and its size, passed BY VALUE: a captured enqueue writes the same buffer on every
+ *                  replay.  out_cap < sz4_cq_bound(q): SZ4_E_CAPACITY before any device work.  No store lands
+ *                  at or beyond d_out + sz4_cq_bound(q)
+ *   d_block_ptrs, d_block_sizes, d_status   device tables of `count` entries, written by the kernels: the
+ *                  address of item i's bare block inside d_out, its length (size word included, stored flag
+ *                  masked off; 0 for an empty item, whose address is where the next block starts), and
+ *                  SZ4_ITEM_OK, SZ4_ITEM_ARG or SZ4_ITEM_INTERNAL.  SZ4_ITEM_INTERNAL is given to every item,
+ *                  with size 0, when a capacity invariant of the pipeline failed (SZ4_E_DEVICE from the
+ *                  synchronous calls)
+ *   d_total        device uint64_t receiving the bytes written to d_out (the sum of the sizes), or NULL
+ * The blocks lie back to back in caller order and are byte for byte those of sz4_compress_batch_typed_device
+ * on the same items: the reference's block of split(item, width).
+ * Returns SZ4_OK once enqueued; SZ4_E_ARG for a null queue, d_src, d_out or result table; SZ4_E_DEVICE for a
+ * launch error. */
+int sz4_cq_enqueue(sz4_cq* q, const void* const* d_src, void* d_out, uint64_t out_cap, uint64_t* d_block_ptrs,
+                   uint32_t* d_block_sizes, uint32_t* d_status, uint64_t* d_total, void* stream);
 
 /* Whole-stream compression with the exact semantics of
  * smallz4::lz4(getBytes, sendBytes, maxChainLength, dictionary, useLegacyFormat)

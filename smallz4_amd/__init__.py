@@ -17,6 +17,8 @@ plus the data-parallel entry point the GPU is built for:
         -> the same for items of fixed-width elements, split into byte planes (planes.py) on the way
     Compressor().decode_queue(max_items, max_src_bytes) -> DecodeQueue.enqueue(...) / tensor_tables(ct, out)
         -> the batch decoders as an enqueue over device tables: no host synchronisation, graph-capturable
+    Compressor().compress_queue(sizes, elems, max_chain_length) -> CompressQueue.enqueue(...) / tensor_tables(t)
+        -> the typed batch compressor as an enqueue for a fixed set of item sizes, graph-capturable as well
 
 All compression runs in the HIP library smallz4_amd/lib/libsmallz4_amd.so; there
 is no CPU fallback.
@@ -162,6 +164,80 @@ class DecodeQueue:
             table([dst + k * ct.chunk_bytes for k in range(count)], torch.int64), table(caps, torch.int32),
             table([e] * count, torch.uint8), torch.zeros(count, dtype=torch.int32, device=dev),
             torch.zeros(count, dtype=torch.int32, device=dev), count, (ct.blocks, out))
+
+
+class CompressQueue:
+    """An enqueue-only batch compressor (sz4_cq_*): the item count, sizes, widths and level are fixed here; the
+    sources come from a device table of pointers, the blocks go to one output buffer and their addresses, sizes
+    and statuses to device tables, with no host synchronisation -- an enqueue can be captured in a graph
+    (torch.cuda.graph) and replayed after the pointer table or the data was rewritten.  block_ptrs and
+    block_sizes are a DecodeQueue's src_ptrs and src_sizes.  Holds its scratch (about 50 bytes per staged byte)
+    until close(); close it before its Compressor, and after every graph captured from it is gone."""
+
+    def __init__(self, comp: "Compressor", sizes, elems=None, max_chain_length: int = MaxChainLength):
+        self._comp = comp
+        self._lib = comp._lib
+        self.device = comp.device
+        self.sizes = [int(x) for x in sizes]
+        self.elems = None if elems is None else [int(x) for x in elems]
+        self.count = len(self.sizes)
+        if self.elems is not None and len(self.elems) != self.count:
+            raise ValueError("sizes and elems differ in length")
+        if any(not 0 <= x < 1 << 32 for x in self.sizes):
+            raise ValueError("an item size is not a uint32")
+        z = (ctypes.c_uint32 * max(self.count, 1))(*self.sizes)
+        w = None
+        if self.elems is not None:
+            w = (ctypes.c_uint8 * max(self.count, 1))(*[x & 0xFF if 0 <= x < 256 else 0 for x in self.elems])
+        h = ctypes.c_void_p()
+        comp._check(self._lib.sz4_cq_create(comp._h, z, w, self.count, int(max_chain_length), ctypes.byref(h)), "sz4_cq_create")
+        self._h = h
+        self.bound = int(self._lib.sz4_cq_bound(h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if self._comp._h:  # a closed Compressor has released the scratch already
+                self._lib.sz4_cq_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def enqueue(self, src_ptrs, out, block_ptrs, block_sizes, status, total=None, stream=None):
+        """Item i, sizes[i] bytes of width elems[i] at address src_ptrs[i], is compressed into `out` (a uint8
+        device tensor of at least `bound` bytes); block_ptrs[i], block_sizes[i] and status[i] (SZ4_ITEM_*) and
+        total[0] receive the result when the stream gets there (see sz4_cq_enqueue).  Device tensors: int64
+        pointers and total, int32 sizes and statuses.  stream: a raw HIP stream (default: torch's current one)."""
+        import torch
+        table = DecodeQueue._table
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.sz4_cq_enqueue(
+            self._h, table(src_ptrs, torch.int64, self.count, "src_ptrs"), table(out, torch.uint8, 0, "out"), out.numel(),
+            table(block_ptrs, torch.int64, self.count, "block_ptrs"), table(block_sizes, torch.int32, self.count, "block_sizes"),
+            table(status, torch.int32, self.count, "status"), None if total is None else table(total, torch.int64, 1, "total"),
+            ctypes.c_void_p(stream))
+        if rc != _native.SZ4_OK:
+            raise _native.NativeError(f"sz4_cq_enqueue failed ({rc})")
+
+    def tensor_tables(self, t):
+        """The source pointer table (int64, on the device) for the contiguous device tensor `t` cut into the
+        queue's items in order: sum(sizes) must be t's bytes.  The table points into t, which the caller
+        keeps alive and may rewrite in place between enqueues."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not t.is_contiguous() or t.device != dev:
+            raise TypeError("t must be a contiguous tensor on the queue's device")
+        if t.numel() * t.element_size() != sum(self.sizes):
+            raise ValueError("the queue's items do not cover the tensor")
+        ptrs, at = [], t.data_ptr()
+        for n in self.sizes:
+            ptrs.append(at)
+            at += n
+        return torch.tensor(ptrs, dtype=torch.int64).to(dev)
 
 
 class Compressor:
@@ -521,6 +597,12 @@ class Compressor:
         """An enqueue-only batch decoder for up to max_items items of max_src_bytes of blocks in all per
         enqueue (sz4_dq_create); its scratch counts as this context's until the queue is closed."""
         return DecodeQueue(self, max_items, max_src_bytes)
+
+    def compress_queue(self, sizes, elems=None, max_chain_length: int = MaxChainLength) -> "CompressQueue":
+        """An enqueue-only batch compressor for items of these sizes and element widths (None: every width 1)
+        at this level (0 or 7 .. 65535) (sz4_cq_create); its scratch counts as this context's until the queue
+        is closed."""
+        return CompressQueue(self, sizes, elems, max_chain_length)
 
     def last_merge_ms(self) -> float:
         """Device time of the last unlz4_batch_typed_device call's merge kernel (with set_timing on)."""

@@ -18,7 +18,7 @@ SZ4_E_CAPACITY = -3
 SZ4_E_CORRUPT = -6
 SZ4_E_DEVICE = -2
 SZ4_E_NOMEM = -4
-# per-item statuses of the decode queue (sz4_dq_enqueue)
+# per-item statuses of the decode queue (sz4_dq_enqueue) and the compress queue (sz4_cq_enqueue)
 SZ4_ITEM_OK = 0
 SZ4_ITEM_CORRUPT = 1
 SZ4_ITEM_CAPACITY = 2
@@ -60,6 +60,11 @@ SIGNATURES = {
     "sz4_dq_create": (_i32, [_vp, _u32, _u64, ctypes.POINTER(_vp)]),
     "sz4_dq_destroy": (None, [_vp]),
     "sz4_dq_enqueue": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    # compress queue: host sizes and widths at creation, device tables at every enqueue
+    "sz4_cq_create": (_i32, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(ctypes.c_uint8), _u32, _u32, ctypes.POINTER(_vp)]),
+    "sz4_cq_destroy": (None, [_vp]),
+    "sz4_cq_bound": (_u64, [_vp]),
+    "sz4_cq_enqueue": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "sz4_lz4": (_i32, [_vp, _vp, _u64, _u32, _vp, _u64, _i32, _vp, _u64, ctypes.POINTER(_u64)]),
     "sz4_lz4_bound": (_u64, [_u64, _i32]),
     "sz4_lz4_stream": (_i32, [_vp, GET_BYTES, SEND_BYTES, _u32, _vp, _u64, _i32, _vp]),

@@ -6,6 +6,8 @@
 //                   pipeline runs (items whose window fits the finders' LDS, and items whose does not)
 //   k_batch_merge   the inverse of the split, after the batch decoder (sz4_unlz4_batch_typed_device)
 // All are copies, bound by memory: 16-byte accesses on the aligned side, work cut by bytes.
+//   k_cq_items, k_cq_finish  the compress queue's ends (sz4_cq_enqueue): the caller's device pointer table
+//                   into the gather's item table, and the run's offsets and sizes out to the caller's tables
 #include <hip/hip_runtime.h>
 
 #include "sz4_internal.h"
@@ -332,7 +334,95 @@ __global__ __launch_bounds__(kGatherThreads) void k_batch_merge(const BatchTyped
   }
 }
 
+// ---- compress queue: the two ends of an enqueue ------------------------------------------------------------
+// One thread per caller item.  A non-empty item's source goes into its block's entry of the run's item table,
+// with the size the gather is to copy: the block's, or 0 for a null source (the item is then staged as zeros
+// and reported as kItemArg).  An empty item's source entry is not read.
+// The kernel also clears what a synchronous run clears with memsets before its first kernel -- the status
+// word, every block's longFlag, the ghost slot's interval count (a queue's first block has no predecessor)
+// and, in a run without blocks, the body's size: a memset captured in a graph was seen to store other bytes
+// than its value from the second replay on, so an enqueue issues kernels only.
+template <typename Item>
+__global__ __launch_bounds__(256) void k_cq_items(const uint64_t* __restrict__ src, const uint32_t* __restrict__ map,
+                                                  uint32_t count, uint32_t nblocks, const Block* __restrict__ blocks,
+                                                  Item* __restrict__ items, uint32_t* __restrict__ status,
+                                                  int* __restrict__ pipeStatus, uint32_t* __restrict__ longFlag,
+                                                  uint32_t* __restrict__ ivCount, uint64_t* __restrict__ offsets)
+{
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) {
+    *pipeStatus = 0;
+    ivCount[nblocks] = 0;
+    if (!nblocks) offsets[0] = 0;
+  }
+  if (i >= count) return;
+  const uint32_t b = map[i];
+  uint32_t st = kItemOk;
+  if (!(b & kCqEmpty)) {
+    const uint64_t p = src[i];
+    if (!p) st = kItemArg;
+    items[b].src = p;
+    items[b].size = p ? (decltype(items[b].size))(blocks[b].end - blocks[b].start) : 0;
+    longFlag[b] = 0;
+  }
+  status[i] = st;
+}
+
+// zeroes `words` 16-byte words at p (the pass-2 marker bits, which the finders OR into)
+__global__ __launch_bounds__(256) void k_cq_zero(uint4* __restrict__ p, uint64_t words)
+{
+  for (uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x; w < words; w += (uint64_t)gridDim.x * 256)
+    p[w] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// A grid-stride loop over the caller's items: block b lies at out + offsets[b] and is blockBytes[b] long (top
+// bit: stored); an empty item gets the address where the next block starts (offsets[nblocks] is the body's
+// size) and size 0.  A run whose capacity invariant failed has no valid block: every item is kItemInternal
+// with size 0 at `out`, and the total is 0.
+__global__ __launch_bounds__(256) void k_cq_finish(const uint32_t* __restrict__ map, uint32_t count, uint32_t nblocks,
+                                                   const uint32_t* __restrict__ blockBytes,
+                                                   const uint64_t* __restrict__ offsets, const int* __restrict__ pipeStatus,
+                                                   uint8_t* out, uint64_t* __restrict__ blockPtrs,
+                                                   uint32_t* __restrict__ blockSizes, uint32_t* __restrict__ status,
+                                                   uint64_t* __restrict__ total)
+{
+  const bool bad = (*pipeStatus & kStInvariant) != 0;
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < count; i += gridDim.x * 256) {
+    const uint32_t m = map[i], b = m & ~kCqEmpty;
+    blockPtrs[i] = reinterpret_cast<uint64_t>(out) + (bad ? 0 : offsets[b]);
+    blockSizes[i] = bad || (m & kCqEmpty) ? 0u : blockBytes[b] & 0x7FFFFFFFu;
+    if (bad) status[i] = kItemInternal;
+  }
+  if (total && blockIdx.x == 0 && threadIdx.x == 0) *total = bad ? 0 : offsets[nblocks];
+}
+
 }  // namespace
+
+void launch_cq_items(const CqTables& T, const PipeArgs& P, void* items, bool typed, hipStream_t s)
+{
+  const dim3 grid((T.count + 255) / 256), block(256);
+  if (typed)
+    hipLaunchKernelGGL(k_cq_items<BatchTyped>, grid, block, 0, s, T.src, T.map, T.count, P.nblocks, P.blocks,
+                       static_cast<BatchTyped*>(items), T.status, P.status, P.longFlag, P.ivCount, P.offsets);
+  else
+    hipLaunchKernelGGL(k_cq_items<BatchItem>, grid, block, 0, s, T.src, T.map, T.count, P.nblocks, P.blocks,
+                       static_cast<BatchItem*>(items), T.status, P.status, P.longFlag, P.ivCount, P.offsets);
+}
+
+void launch_cq_zero(void* p, uint64_t bytes, hipStream_t s)
+{
+  const uint64_t words = (bytes + 15) / 16, groups = (words + 255) / 256;
+  if (words)
+    hipLaunchKernelGGL(k_cq_zero, dim3((uint32_t)(groups < kGatherGrid ? groups : kGatherGrid)), dim3(256), 0, s,
+                       static_cast<uint4*>(p), words);
+}
+
+void launch_cq_finish(const CqTables& T, const PipeArgs& P, hipStream_t s)
+{
+  const uint32_t groups = (T.count + 255) / 256;
+  hipLaunchKernelGGL(k_cq_finish, dim3(groups < kGatherGrid ? groups : kGatherGrid), dim3(256), 0, s, T.map, T.count, P.nblocks,
+                     P.blockBytes, P.offsets, P.status, T.out, T.blockPtrs, T.blockSizes, T.status, T.total);
+}
 
 void launch_batch_gather(const BatchItem* items, uint32_t n, uint8_t* staged, uint64_t stagedBytes, hipStream_t s)
 {

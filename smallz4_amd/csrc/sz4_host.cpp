@@ -71,6 +71,139 @@ uint32_t xxh32_small(const uint8_t* d, size_t n)
   return h;
 }
 
+// Everything one pipeline run names on the device, and the plan it runs: the context holds one for its calls,
+// a compress queue another (held) one, so that neither moves or overwrites what the other's kernels read.
+// Every DevBuf is constructed on the owner's budget and enters its list there.
+struct Pipe {
+  DevBuf staged, blocks, segs, iv, ivCount, rank, mlen, mdist;
+  DevBuf cost, ntok, blockBytes, offsets, status;
+  DevBuf dpSegs, reach, segState, walkSegs, walkState;
+  DevBuf longFlag, longBits, segLong, segTail;
+  DevBuf dpRec;       // the parallel parse-boundary repair's records
+  DevBuf work;        // the arrays whose lifetimes do not overlap, at plan.off (Plan::work_layout)
+  DevBuf batchItems;  // ragged runs: the gather's item table
+  // The block plan of the current run: one object for every kind of call, rebuilt when its key differs.
+  // Its device copy (blocks, segments, parse segments, walk sub-segments) is fresh while it holds this
+  // version of the plan at these four addresses: repeated calls on the same shape skip the uploads
+  Plan plan;
+  uint64_t uploadedVersion = ~0ull;
+  const void* uploadedAt[4] = {};
+
+  explicit Pipe(Budget& b, bool keep = false)
+      : staged(b, keep), blocks(b, keep), segs(b, keep), iv(b, keep), ivCount(b, keep), rank(b, keep), mlen(b, keep),
+        mdist(b, keep), cost(b, keep), ntok(b, keep), blockBytes(b, keep), offsets(b, keep), status(b, keep),
+        dpSegs(b, keep), reach(b, keep), segState(b, keep), walkSegs(b, keep), walkState(b, keep), longFlag(b, keep),
+        longBits(b, keep), segLong(b, keep), segTail(b, keep), dpRec(b, keep), work(b, keep), batchItems(b, keep) {}
+  template <class T>
+  T* work_at(uint64_t off) const { return reinterpret_cast<T*>(work.as<uint8_t>() + off); }
+  uint32_t* sel() const { return work.as<uint32_t>(); }
+  // the scratch of a run of the plan over `stagedBytes` of staged input (staging and the item table are the caller's)
+  hipError_t reserve(uint64_t stagedBytes);
+  // the launchers' view of the buffers for the plan.  A reserve can move a buffer, so this runs after every
+  // reserve of the call (reserve; the dictionary's own reserves move only dict* buffers)
+  PipeArgs args(uint32_t maxChain, const uint8_t* in, uint8_t* out, uint64_t hdrLen) const;
+  // the plan's four tables to their buffers, on s
+  hipError_t upload_plan(hipStream_t s) const;
+  // a pipe that ends before its budget's owner does (a compress queue's)
+  void detach()
+  {
+    for (DevBuf* b : {&staged, &blocks, &segs, &iv, &ivCount, &rank, &mlen, &mdist, &cost, &ntok, &blockBytes, &offsets,
+                      &status, &dpSegs, &reach, &segState, &walkSegs, &walkState, &longFlag, &longBits, &segLong, &segTail,
+                      &dpRec, &work, &batchItems})
+      b->detach();
+  }
+};
+
+hipError_t Pipe::reserve(uint64_t stagedBytes)
+{
+  const uint64_t nb = plan.blocks.size();
+  hipError_t e = hipSuccess;
+  (e = blocks.reserve(nb * sizeof(Block) + 64)) ||
+      (e = segs.reserve(plan.segs.size() * sizeof(Segment) + 64)) ||
+      (e = iv.reserve((nb + 1) * kMaxIv * sizeof(Interval) + 64)) ||
+      (e = ivCount.reserve((nb + 1) * 4 + 64)) ||
+      (e = rank.reserve(plan.rankTotal * 4 + 64)) ||
+      (e = mlen.reserve(stagedBytes * 4 + 64)) ||
+      (e = mdist.reserve(stagedBytes * 2 + 64)) ||
+      (e = cost.reserve((stagedBytes + nb + 8) * 4)) ||
+      (e = ntok.reserve(nb * 4 + 64)) ||
+      (e = blockBytes.reserve(nb * 4 + 64)) ||
+      (e = offsets.reserve((nb + 1) * 8 + 64)) ||
+      (e = status.reserve(64)) ||
+      (e = dpSegs.reserve(plan.dp.size() * sizeof(DpSeg) + 64)) ||
+      (e = reach.reserve(stagedBytes * 4 + 64)) ||
+      (e = segState.reserve(plan.dp.size() * sizeof(uint4) + 64)) ||
+      (e = dpRec.reserve(plan.dp.size() * sizeof(uint4) + 64)) ||
+      (e = walkSegs.reserve(plan.walk.size() * sizeof(uint2) + 64)) ||
+      (e = walkState.reserve(plan.walk.size() * sizeof(uint4) + 64)) ||
+      (e = longFlag.reserve(nb * 4 + 64)) ||
+      (e = longBits.reserve(stagedBytes / 8 + 64)) ||
+      (e = segLong.reserve(plan.segs.size() * 4 + 64)) ||
+      (e = segTail.reserve(plan.segs.size() * 8 + 64)) ||
+      (e = work.reserve(plan.work_layout(stagedBytes)));
+  return e;
+}
+
+PipeArgs Pipe::args(uint32_t maxChain, const uint8_t* in, uint8_t* out, uint64_t hdrLen) const
+{
+  PipeArgs a{};
+  a.in = in;
+  a.blocks = blocks.as<Block>();
+  a.nblocks = (uint32_t)plan.blocks.size();
+  a.segs = segs.as<Segment>();
+  a.nsegs = (uint32_t)plan.segs.size();
+  a.dpSegs = dpSegs.as<DpSeg>();
+  a.ndp = (uint32_t)plan.dp.size();
+  a.maxDpCount = plan.maxDpCount;
+  a.walkSegs = walkSegs.as<uint2>();
+  a.nwalk = (uint32_t)plan.walk.size();
+  a.maxChain = maxChain;
+  a.iv = iv.as<Interval>();
+  a.ivCount = ivCount.as<uint32_t>();
+  a.mlen = mlen.as<uint32_t>();
+  a.mdist = mdist.as<uint16_t>();
+  a.sel = sel();
+  a.cost = cost.as<uint32_t>();
+  a.reach = reach.as<uint32_t>();
+  a.longFlag = longFlag.as<uint32_t>();
+  a.longBits = longBits.as<uint32_t>();
+  a.segLong = segLong.as<uint32_t>();
+  a.segTail = segTail.as<uint64_t>();
+  a.rank = rank.as<uint32_t>();
+  const Plan::WorkOffsets& off = plan.off;
+  a.elemA = work.as<uint2>();
+  a.elemB = work_at<uint2>(off.elemB);
+  a.rmqUp = work_at<uint32_t>(off.rmqUp);
+  a.rmqDown = work_at<uint32_t>(off.rmqDown);
+  a.dpSide = work_at<uint2>(off.side);
+  a.dpRec = dpRec.as<uint4>();
+  a.segState = segState.as<uint4>();
+  a.lazySlots = work_at<uint32_t>(off.lazy);
+  a.walkSlots = work_at<uint32_t>(off.walk);
+  a.walkState = walkState.as<uint4>();
+  a.tokens = work_at<Token>(off.tok);
+  a.ntok = ntok.as<uint32_t>();
+  a.blockBytes = blockBytes.as<uint32_t>();
+  a.offsets = offsets.as<uint64_t>();
+  a.status = status.as<int>();
+  a.ldsWindow = plan.ldsWindow;
+  a.out = out;
+  a.headerLen = hdrLen;
+  // optimal levels tokenize the parse's choices, greedy/lazy levels the (skip-filtered) matches
+  a.chosen = maxChain > (uint32_t)kGreedyMax ? a.sel : a.mlen;
+  return a;
+}
+
+hipError_t Pipe::upload_plan(hipStream_t s) const
+{
+  hipError_t e = hipSuccess;
+  (e = hipMemcpyAsync(blocks.p, plan.blocks.data(), plan.blocks.size() * sizeof(Block), hipMemcpyHostToDevice, s)) ||
+      (e = hipMemcpyAsync(segs.p, plan.segs.data(), plan.segs.size() * sizeof(Segment), hipMemcpyHostToDevice, s)) ||
+      (e = hipMemcpyAsync(dpSegs.p, plan.dp.data(), plan.dp.size() * sizeof(DpSeg), hipMemcpyHostToDevice, s)) ||
+      (e = hipMemcpyAsync(walkSegs.p, plan.walk.data(), plan.walk.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
+  return e;
+}
+
 }  // namespace
 
 struct sz4_ctx {
@@ -86,15 +219,7 @@ struct sz4_ctx {
   // Device scratch.  Every DevBuf is constructed on `budget` and enters its list there: accounting, the device
   // limit, shed(), sz4_trim and sz4_destroy see a buffer because it is declared, and nowhere else is it named.
   Budget budget;
-  DevBuf staged{budget}, blocks{budget}, segs{budget}, iv{budget}, ivCount{budget}, rank{budget}, mlen{budget}, mdist{budget};
-  DevBuf cost{budget}, ntok{budget}, blockBytes{budget}, offsets{budget}, status{budget};
-  DevBuf dpSegs{budget}, reach{budget}, segState{budget}, walkSegs{budget}, walkState{budget};
-  DevBuf longFlag{budget}, longBits{budget}, segLong{budget}, segTail{budget};
-  DevBuf dpRec{budget};             // the parallel parse-boundary repair's records
-  DevBuf work{budget};              // the arrays whose lifetimes do not overlap, at plan.off (Plan::work_layout)
-  template <class T>
-  T* work_at(uint64_t off) const { return reinterpret_cast<T*>(work.as<uint8_t>() + off); }
-  uint32_t* sel() const { return work.as<uint32_t>(); }
+  Pipe pipe{budget};  // the pipeline's buffers and the block plan of the current run
   DevBuf dictLast{budget}, dictPrevH{budget}, dictPrevX{budget};  // dictionary mode: the reference's hash table and both chains
   // dictionary mode on the whole GPU (sz4_dict.hip)
   DevBuf dictPH{budget}, dictPE{budget}, dictKeys{budget}, dictTemp{budget}, dictSc{budget}, dictSnap{budget}, dictRuns{budget};
@@ -121,9 +246,9 @@ struct sz4_ctx {
   DevBuf unBlk{budget}, unMeta{budget}, unFlags{budget}, unFrame{budget}, unDict{budget}, unOut{budget}, unSeq{budget};
   DevBuf unSubs{budget}, unMasks{budget}, unImage{budget};
   DevBuf unIx{budget};                    // decoder: the parallel frame index's candidates and successors
-  // ragged batch API: the gather's item table, the block mover's table and the staging area of a piece that
-  // runs as two pipeline runs (sz4_compress_batch_device); the batch decoder's extent table
-  DevBuf batchItems{budget}, batchMoves{budget}, batchTmp{budget}, unBatch{budget};
+  // ragged batch API: the block mover's table and the staging area of a piece that runs as two pipeline
+  // runs (sz4_compress_batch_device); the batch decoder's extent table
+  DevBuf batchMoves{budget}, batchTmp{budget}, unBatch{budget};
   // typed batch decoder (sz4_unlz4_batch_typed_device): the decoded split items, and k_batch_merge's item table
   DevBuf unPlanes{budget}, mergeItems{budget};
   hipEvent_t evGather[2] = {};  // timing: around k_batch_gather / k_batch_gather_planes
@@ -139,12 +264,6 @@ struct sz4_ctx {
   int unSplitMode = getenv("SZ4_UNLZ4_SPLIT") ? atoi(getenv("SZ4_UNLZ4_SPLIT")) : -1;  // -1 auto, 0 never, 1 always
   bool dictSerial = getenv("SZ4_DICT_SERIAL") != nullptr;  // A/B and tests: the in-order replay for every chunk
 
-  // The block plan of the current run: one object for every kind of call, rebuilt when its key differs.
-  // Its device copy (blocks, segments, parse segments, walk sub-segments) is fresh while it holds this
-  // version of the plan at these four addresses: repeated calls on the same shape skip the uploads
-  Plan plan;
-  uint64_t uploadedVersion = ~0ull;
-  const void* uploadedAt[4] = {};
   std::vector<uint32_t> hostBytes;
 
   hipStream_t stream = nullptr;  // the stream path's compute stream
@@ -175,32 +294,7 @@ namespace {
 
 int reserve_all(sz4_ctx* c, uint64_t stagedBytes)
 {
-  const uint64_t nb = c->plan.blocks.size();
-  hipError_t e = hipSuccess;
-  if ((e = c->blocks.reserve(nb * sizeof(Block) + 64)) ||
-      (e = c->segs.reserve(c->plan.segs.size() * sizeof(Segment) + 64)) ||
-      (e = c->iv.reserve((nb + 1) * kMaxIv * sizeof(Interval) + 64)) ||
-      (e = c->ivCount.reserve((nb + 1) * 4 + 64)) ||
-      (e = c->rank.reserve(c->plan.rankTotal * 4 + 64)) ||
-      (e = c->mlen.reserve(stagedBytes * 4 + 64)) ||
-      (e = c->mdist.reserve(stagedBytes * 2 + 64)) ||
-      (e = c->cost.reserve((stagedBytes + nb + 8) * 4)) ||
-      (e = c->ntok.reserve(nb * 4 + 64)) ||
-      (e = c->blockBytes.reserve(nb * 4 + 64)) ||
-      (e = c->offsets.reserve((nb + 1) * 8 + 64)) ||
-      (e = c->status.reserve(64)) ||
-      (e = c->dpSegs.reserve(c->plan.dp.size() * sizeof(DpSeg) + 64)) ||
-      (e = c->reach.reserve(stagedBytes * 4 + 64)) ||
-      (e = c->segState.reserve(c->plan.dp.size() * sizeof(uint4) + 64)) ||
-      (e = c->dpRec.reserve(c->plan.dp.size() * sizeof(uint4) + 64)) ||
-      (e = c->walkSegs.reserve(c->plan.walk.size() * sizeof(uint2) + 64)) ||
-      (e = c->walkState.reserve(c->plan.walk.size() * sizeof(uint4) + 64)) ||
-      (e = c->longFlag.reserve(nb * 4 + 64)) ||
-      (e = c->longBits.reserve(stagedBytes / 8 + 64)) ||
-      (e = c->segLong.reserve(c->plan.segs.size() * 4 + 64)) ||
-      (e = c->segTail.reserve(c->plan.segs.size() * 8 + 64)) ||
-      (e = c->work.reserve(c->plan.work_layout(stagedBytes))))
-    return c->fail(SZ4_E_NOMEM, "device allocation", e);
+  if (hipError_t e = c->pipe.reserve(stagedBytes)) return c->fail(SZ4_E_NOMEM, "device allocation", e);
   return SZ4_OK;
 }
 
@@ -227,77 +321,20 @@ struct RunMode {
   bool ghost = false;     // the first block's B.prev is the ghost slot: upload the context's ghostIv into it
 };
 
-// the launchers' view of the context's buffers for the current plan.  A reserve can move a buffer, so this
-// runs after every reserve of the call (reserve_all; the dictionary's own reserves move only dict* buffers)
-PipeArgs pipe_args(const sz4_ctx* c, uint32_t maxChain, const uint8_t* in, uint8_t* out, uint64_t hdrLen)
-{
-  PipeArgs a{};
-  a.in = in;
-  a.blocks = c->blocks.as<Block>();
-  a.nblocks = (uint32_t)c->plan.blocks.size();
-  a.segs = c->segs.as<Segment>();
-  a.nsegs = (uint32_t)c->plan.segs.size();
-  a.dpSegs = c->dpSegs.as<DpSeg>();
-  a.ndp = (uint32_t)c->plan.dp.size();
-  a.maxDpCount = c->plan.maxDpCount;
-  a.walkSegs = c->walkSegs.as<uint2>();
-  a.nwalk = (uint32_t)c->plan.walk.size();
-  a.maxChain = maxChain;
-  a.iv = c->iv.as<Interval>();
-  a.ivCount = c->ivCount.as<uint32_t>();
-  a.mlen = c->mlen.as<uint32_t>();
-  a.mdist = c->mdist.as<uint16_t>();
-  a.sel = c->sel();
-  a.cost = c->cost.as<uint32_t>();
-  a.reach = c->reach.as<uint32_t>();
-  a.longFlag = c->longFlag.as<uint32_t>();
-  a.longBits = c->longBits.as<uint32_t>();
-  a.segLong = c->segLong.as<uint32_t>();
-  a.segTail = c->segTail.as<uint64_t>();
-  a.rank = c->rank.as<uint32_t>();
-  const Plan::WorkOffsets& off = c->plan.off;
-  a.elemA = c->work.as<uint2>();
-  a.elemB = c->work_at<uint2>(off.elemB);
-  a.rmqUp = c->work_at<uint32_t>(off.rmqUp);
-  a.rmqDown = c->work_at<uint32_t>(off.rmqDown);
-  a.dpSide = c->work_at<uint2>(off.side);
-  a.dpRec = c->dpRec.as<uint4>();
-  a.segState = c->segState.as<uint4>();
-  a.lazySlots = c->work_at<uint32_t>(off.lazy);
-  a.walkSlots = c->work_at<uint32_t>(off.walk);
-  a.walkState = c->walkState.as<uint4>();
-  a.tokens = c->work_at<Token>(off.tok);
-  a.ntok = c->ntok.as<uint32_t>();
-  a.blockBytes = c->blockBytes.as<uint32_t>();
-  a.offsets = c->offsets.as<uint64_t>();
-  a.status = c->status.as<int>();
-  a.ldsWindow = c->plan.ldsWindow;
-  a.out = out;
-  a.headerLen = hdrLen;
-  // optimal levels tokenize the parse's choices, greedy/lazy levels the (skip-filtered) matches
-  a.chosen = maxChain > (uint32_t)kGreedyMax ? a.sel : a.mlen;
-  return a;
-}
-
 // run the kernel pipeline over the planned blocks of the staged input `in`; frame goes to `out`.
 // finish = false: return once every kernel is enqueued (pipeline_finish collects the result)
 int run_pipeline(sz4_ctx* c, const RunMode& mode, uint32_t maxChain, const uint8_t* in, const uint8_t* hdr, uint64_t hdrLen,
                  bool endMark, uint8_t* out, uint64_t outCap, uint64_t* outSize, hipStream_t s, bool finish = true)
 {
-  const uint32_t nb = (uint32_t)c->plan.blocks.size();
+  const uint32_t nb = (uint32_t)c->pipe.plan.blocks.size();
   c->lastChain = maxChain;
   hipError_t e;
-  const void* at[4] = {c->blocks.p, c->segs.p, c->dpSegs.p, c->walkSegs.p};
-  const bool fresh = c->uploadedVersion == c->plan.version && memcmp(at, c->uploadedAt, sizeof at) == 0;
-  if (!fresh &&
-      ((e = hipMemcpyAsync(c->blocks.p, c->plan.blocks.data(), nb * sizeof(Block), hipMemcpyHostToDevice, s)) ||
-       (e = hipMemcpyAsync(c->segs.p, c->plan.segs.data(), c->plan.segs.size() * sizeof(Segment), hipMemcpyHostToDevice, s)) ||
-       (e = hipMemcpyAsync(c->dpSegs.p, c->plan.dp.data(), c->plan.dp.size() * sizeof(DpSeg), hipMemcpyHostToDevice, s)) ||
-       (e = hipMemcpyAsync(c->walkSegs.p, c->plan.walk.data(), c->plan.walk.size() * sizeof(uint2), hipMemcpyHostToDevice, s))))
-    return c->fail(SZ4_E_DEVICE, "upload plan", e);
-  c->uploadedVersion = c->plan.version;
-  memcpy(c->uploadedAt, at, sizeof at);
-  const PipeArgs P = pipe_args(c, maxChain, in, out, hdrLen);
+  const void* at[4] = {c->pipe.blocks.p, c->pipe.segs.p, c->pipe.dpSegs.p, c->pipe.walkSegs.p};
+  const bool fresh = c->pipe.uploadedVersion == c->pipe.plan.version && memcmp(at, c->pipe.uploadedAt, sizeof at) == 0;
+  if (!fresh && (e = c->pipe.upload_plan(s))) return c->fail(SZ4_E_DEVICE, "upload plan", e);
+  c->pipe.uploadedVersion = c->pipe.plan.version;
+  memcpy(c->pipe.uploadedAt, at, sizeof at);
+  const PipeArgs P = c->pipe.args(maxChain, in, out, hdrLen);
   if ((e = hipMemsetAsync(P.status, 0, 4, s)) || (e = hipMemsetAsync(P.longFlag, 0, nb * 4, s)))
     return c->fail(SZ4_E_DEVICE, "upload plan", e);
   // ghost slot nb: the previous chunk's last block (only its intervals are read, through B.prev).  The
@@ -320,7 +357,7 @@ int run_pipeline(sz4_ctx* c, const RunMode& mode, uint32_t maxChain, const uint8
         (e = c->dictPrevX.reserve(2 * 65536)))
       return c->fail(SZ4_E_NOMEM, "dictionary tables", e);
     DictArgs A{P};
-    A.hBlocks = c->plan.blocks.data();
+    A.hBlocks = c->pipe.plan.blocks.data();
     A.dictBack = (uint32_t)mode.dictBack;
     A.cont = mode.cont;
     A.shift = mode.shift;
@@ -332,9 +369,9 @@ int run_pipeline(sz4_ctx* c, const RunMode& mode, uint32_t maxChain, const uint8
     if (c->dictSerial) {
       launch_dict(A, s);  // A/B and tests: the reference's loop replayed in order by one wavefront
     } else {
-      const uint64_t staged = c->plan.blocks.back().end + 64;
+      const uint64_t staged = c->pipe.plan.blocks.back().end + 64;
       uint64_t maxBlock = 0;
-      for (const Block& B : c->plan.blocks) maxBlock = std::max<uint64_t>(maxBlock, B.end - B.start);
+      for (const Block& B : c->pipe.plan.blocks) maxBlock = std::max<uint64_t>(maxBlock, B.end - B.start);
       // rocPRIM's scratch size, queried once per context on its own device (0: the query failed)
       if (!c->dictTempBytes && !(c->dictTempBytes = dict_sort_temp_bytes()))
         return c->fail(SZ4_E_DEVICE, "dictionary sort: scratch size query");
@@ -343,7 +380,7 @@ int run_pipeline(sz4_ctx* c, const RunMode& mode, uint32_t maxChain, const uint8
           (e = c->dictKeys.reserve(2 * dict_sort_keys_max() * 8)) || (e = c->dictTemp.reserve(c->dictTempBytes + 64)) ||
           (e = c->dictSc.reserve(dict_sc_bits_bytes(nb, maxBlock))) ||
           (e = c->dictSnap.reserve(lastBytes + 2 * slotBytes)) || (e = c->dictRuns.reserve(dict_run_table_bytes(staged))) ||
-          (e = c->dictLz.reserve(c->plan.walk.size() * dict_lz_mask_bytes_per_walk() + 64)))
+          (e = c->dictLz.reserve(c->pipe.plan.walk.size() * dict_lz_mask_bytes_per_walk() + 64)))
         return c->fail(SZ4_E_NOMEM, "dictionary scratch", e);
       // the carried tables as this chunk found them: a round that finds other shortcut intervals starts
       // again from here (legacy frames carry nothing: every block starts from empty tables)
@@ -403,7 +440,7 @@ int run_pipeline(sz4_ctx* c, const RunMode& mode, uint32_t maxChain, const uint8
     if (maxChain > 0) {
       // k_find_sorted writes every target (shortcut-interval targets "unresolved", for pass 2); its
       // marker bits are OR-ed in
-      if ((e = hipMemsetAsync(P.longBits, 0, c->plan.blocks.back().end / 8 + 8, s)))
+      if ((e = hipMemsetAsync(P.longBits, 0, c->pipe.plan.blocks.back().end / 8 + 8, s)))
         return c->fail(SZ4_E_DEVICE, "clear matches", e);
     }
     mark(c, 2, s);
@@ -441,12 +478,12 @@ int run_pipeline(sz4_ctx* c, const RunMode& mode, uint32_t maxChain, const uint8
 int pipeline_finish(sz4_ctx* c, const uint8_t* hdr, uint64_t hdrLen, bool endMark, uint8_t* out, uint64_t outCap,
                     uint64_t* outSize, hipStream_t s)
 {
-  const uint32_t nb = (uint32_t)c->plan.blocks.size();
+  const uint32_t nb = (uint32_t)c->pipe.plan.blocks.size();
   hipError_t e;
   uint64_t total = 0;
   int status = 0;
-  if ((e = hipMemcpyAsync(&total, c->offsets.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost, s)) ||
-      (e = hipMemcpyAsync(&status, c->status.p, 4, hipMemcpyDeviceToHost, s)) || (e = hipStreamSynchronize(s)))
+  if ((e = hipMemcpyAsync(&total, c->pipe.offsets.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost, s)) ||
+      (e = hipMemcpyAsync(&status, c->pipe.status.p, 4, hipMemcpyDeviceToHost, s)) || (e = hipStreamSynchronize(s)))
     return c->fail(SZ4_E_DEVICE, "pipeline", e);
   if (status & kStInvariant) return c->fail(SZ4_E_DEVICE, "device invariant failed (walk slots / token capacity)");
   const uint64_t size = hdrLen + total + (endMark ? 4 : 0);
@@ -784,7 +821,7 @@ int stream_compress_body(sz4_ctx* c, sz4_get_bytes get, sz4_send_bytes send, uin
     worst.pre = eof ? ch[0].pre : kCarryMax - 1;
     worst.n = span;
     worst.first = eof;
-    c->plan.build_stream(worst.pre, worst.n, worst.first, legacy, dictMode);
+    c->pipe.plan.build_stream(worst.pre, worst.n, worst.first, legacy, dictMode);
     if (int r = reserve_all(c, worst.pre + worst.n + kPad)) return r;
   }
   if (dictMode && ch[0].n) {
@@ -813,7 +850,7 @@ int stream_compress_body(sz4_ctx* c, sz4_get_bytes get, sz4_send_bytes send, uin
     const uint32_t sl = k & 1;
     const StreamChunk& x = ch[sl];
     mode.ghost = !legacy && !x.first && !dictMode;
-    c->plan.build_stream(x.pre, x.n, x.first, legacy, dictMode);
+    c->pipe.plan.build_stream(x.pre, x.n, x.first, legacy, dictMode);
     if (int r = reserve_all(c, x.pre + x.n + kPad)) return r;
     if ((e = hipStreamWaitEvent(c->stream, c->evUp[sl], 0))) return c->fail(SZ4_E_DEVICE, "chunk", e);
     uint64_t unused = 0;
@@ -831,14 +868,14 @@ int stream_compress_body(sz4_ctx* c, sz4_get_bytes get, sz4_send_bytes send, uin
     if (int r = pipeline_finish(c, nullptr, 0, false, c->chunkOut[sl].as<uint8_t>(), c->chunkOut[sl].cap, size, c->stream))
       return r;
     const uint64_t shift = x.shift();
-    const uint32_t nb = (uint32_t)c->plan.blocks.size();
+    const uint32_t nb = (uint32_t)c->pipe.plan.blocks.size();
     if (!legacy && !dictMode) {
       uint32_t cnt = 0;
-      if ((e = hipMemcpyAsync(&cnt, c->ivCount.as<uint32_t>() + (nb - 1), 4, hipMemcpyDeviceToHost, c->stream)) ||
+      if ((e = hipMemcpyAsync(&cnt, c->pipe.ivCount.as<uint32_t>() + (nb - 1), 4, hipMemcpyDeviceToHost, c->stream)) ||
           (e = hipStreamSynchronize(c->stream)))
         return c->fail(SZ4_E_DEVICE, "intervals", e);
       std::vector<Interval> iv(cnt);
-      if (cnt && ((e = hipMemcpyAsync(iv.data(), c->iv.as<Interval>() + (uint64_t)(nb - 1) * kMaxIv, cnt * sizeof(Interval),
+      if (cnt && ((e = hipMemcpyAsync(iv.data(), c->pipe.iv.as<Interval>() + (uint64_t)(nb - 1) * kMaxIv, cnt * sizeof(Interval),
                                       hipMemcpyDeviceToHost, c->stream)) || (e = hipStreamSynchronize(c->stream))))
         return c->fail(SZ4_E_DEVICE, "intervals", e);
       c->ghostIv.clear();
@@ -1117,33 +1154,33 @@ int batch_run(sz4_ctx* c, const std::vector<uint64_t>& idx, const void* const* p
   std::vector<BatchTyped> typed(planes ? nb : 0);
   std::vector<uint64_t> runSizes(nb);
   for (uint32_t k = 0; k < nb; k++) runSizes[k] = sizes[idx[k]];
-  const uint64_t stagedBytes = c->plan.build_ragged(runSizes) + kPad;
+  const uint64_t stagedBytes = c->pipe.plan.build_ragged(runSizes) + kPad;
   for (uint32_t k = 0; k < nb; k++) {
-    const uint64_t at = c->plan.blocks[k].start, n = runSizes[k];
+    const uint64_t at = c->pipe.plan.blocks[k].start, n = runSizes[k];
     if (planes) typed[k] = BatchTyped{(uint64_t)(uintptr_t)ptrs[idx[k]], at, (uint32_t)n, elems[idx[k]]};
     else items[k] = BatchItem{(uint64_t)(uintptr_t)ptrs[idx[k]], at, n};
   }
   hipError_t e = hipSuccess;
   if (int r = reserve_all(c, stagedBytes)) return r;
   static_assert(sizeof(BatchTyped) == sizeof(BatchItem), "one table size for both gathers");
-  if ((e = c->staged.reserve(stagedBytes)) || (e = c->batchItems.reserve(nb * sizeof(BatchItem) + 64)))
+  if ((e = c->pipe.staged.reserve(stagedBytes)) || (e = c->pipe.batchItems.reserve(nb * sizeof(BatchItem) + 64)))
     return c->fail(SZ4_E_NOMEM, "staging", e);
   // the item table goes up with the plan, on the call's stream; `items` lives until the run has finished
-  if ((e = hipMemcpyAsync(c->batchItems.p, planes ? (const void*)typed.data() : (const void*)items.data(), nb * sizeof(BatchItem),
+  if ((e = hipMemcpyAsync(c->pipe.batchItems.p, planes ? (const void*)typed.data() : (const void*)items.data(), nb * sizeof(BatchItem),
                           hipMemcpyHostToDevice, s)))
     return c->fail(SZ4_E_DEVICE, "upload items", e);
   if (c->timing) hipEventRecord(c->evGather[0], s);
-  if (planes) launch_batch_gather_planes(c->batchItems.as<BatchTyped>(), nb, c->staged.as<uint8_t>(), stagedBytes, s);
-  else launch_batch_gather(c->batchItems.as<BatchItem>(), nb, c->staged.as<uint8_t>(), stagedBytes, s);
+  if (planes) launch_batch_gather_planes(c->pipe.batchItems.as<BatchTyped>(), nb, c->pipe.staged.as<uint8_t>(), stagedBytes, s);
+  else launch_batch_gather(c->pipe.batchItems.as<BatchItem>(), nb, c->pipe.staged.as<uint8_t>(), stagedBytes, s);
   if (c->timing) hipEventRecord(c->evGather[1], s);
   uint64_t size = 0;
-  if (int r = run_pipeline(c, RunMode{}, maxChain, c->staged.as<uint8_t>(), nullptr, 0, false, out, outCap, &size, s)) return r;
+  if (int r = run_pipeline(c, RunMode{}, maxChain, c->pipe.staged.as<uint8_t>(), nullptr, 0, false, out, outCap, &size, s)) return r;
   if (c->timing) {
     float ms = 0;
     if (hipEventElapsedTime(&ms, c->evGather[0], c->evGather[1]) == hipSuccess) c->gatherMs += ms;
   }
   bytes.resize(nb);
-  if ((e = hipMemcpy(bytes.data(), c->blockBytes.p, nb * 4ull, hipMemcpyDeviceToHost)))
+  if ((e = hipMemcpy(bytes.data(), c->pipe.blockBytes.p, nb * 4ull, hipMemcpyDeviceToHost)))
     return c->fail(SZ4_E_DEVICE, "block sizes", e);
   return SZ4_OK;
 }
@@ -1241,8 +1278,8 @@ int sz4_create(sz4_ctx** ctx, int device, uint64_t reserve_bytes)
   for (auto& e : c->evMerge) hipEventCreate(&e);
   c->budget.owner = c;
   // a released plan buffer may come back at the same address: upload the plan again
-  c->budget.onShed = [](void* o) { static_cast<sz4_ctx*>(o)->uploadedVersion = ~0ull; };
-  if (reserve_bytes && c->staged.reserve(reserve_bytes + kPad) != hipSuccess) {
+  c->budget.onShed = [](void* o) { static_cast<sz4_ctx*>(o)->pipe.uploadedVersion = ~0ull; };
+  if (reserve_bytes && c->pipe.staged.reserve(reserve_bytes + kPad) != hipSuccess) {
     sz4_destroy(c);
     return SZ4_E_NOMEM;
   }
@@ -1314,9 +1351,9 @@ void sz4_trim(sz4_ctx* c)
   for (hipStream_t x : {c->stream, c->upStream, c->downStream})
     if (x) hipStreamSynchronize(x);
   for (DevBuf* b : c->budget.bufs)
-    if (!b->held) b->release();  // a live decode queue keeps its scratch
+    if (!b->held) b->release();  // a live decode or compress queue keeps its scratch
   for (HostBuf* b : {&c->hostIn[0], &c->hostIn[1], &c->hostOut[0], &c->hostOut[1]}) b->release();
-  c->uploadedVersion = ~0ull;
+  c->pipe.uploadedVersion = ~0ull;
 }
 
 void sz4_set_device_limit(sz4_ctx* c, uint64_t bytes)
@@ -1396,10 +1433,10 @@ int sz4_compress_blocks_device(sz4_ctx* c, const void* d_in, uint64_t n, uint32_
   for (uint64_t off = 0; off < n; off += piece) {
     const uint64_t len = std::min(piece, n - off);
     const bool firstPiece = off == 0, lastPiece = off + len == n;
-    c->plan.build_uniform(len, block_size);
+    c->pipe.plan.build_uniform(len, block_size);
     hipError_t e = hipSuccess;
     int rr = reserve_all(c, len + kPad);
-    if (rr == SZ4_OK && (e = c->staged.reserve(len + kPad))) rr = c->fail(SZ4_E_NOMEM, "staging", e);
+    if (rr == SZ4_OK && (e = c->pipe.staged.reserve(len + kPad))) rr = c->fail(SZ4_E_NOMEM, "staging", e);
     if (rr == SZ4_E_NOMEM && piece > block_size && piece > kPieceFloor) {
       // smaller pieces: the next iteration re-plans this offset with half the piece
       piece = std::max<uint64_t>(block_size, std::max<uint64_t>(kPieceFloor, piece / 2) / block_size * block_size);
@@ -1408,21 +1445,21 @@ int sz4_compress_blocks_device(sz4_ctx* c, const void* d_in, uint64_t n, uint32_
     }
     if (rr) return rr;
     // private padded copy: kernels read 4-byte windows that may run past the caller's buffer
-    if ((e = hipMemcpyAsync(c->staged.p, (const uint8_t*)d_in + off, len, hipMemcpyDeviceToDevice, s)))
+    if ((e = hipMemcpyAsync(c->pipe.staged.p, (const uint8_t*)d_in + off, len, hipMemcpyDeviceToDevice, s)))
       return c->fail(SZ4_E_DEVICE, "stage input", e);
-    if ((e = hipMemsetAsync(c->staged.as<uint8_t>() + len, 0, kPad, s))) return c->fail(SZ4_E_DEVICE, "stage pad", e);
+    if ((e = hipMemsetAsync(c->pipe.staged.as<uint8_t>() + len, 0, kPad, s))) return c->fail(SZ4_E_DEVICE, "stage pad", e);
     uint64_t size = 0;
-    if (int r = run_pipeline(c, RunMode{}, max_chain, c->staged.as<uint8_t>(), hdr, firstPiece ? hl : 0,
+    if (int r = run_pipeline(c, RunMode{}, max_chain, c->pipe.staged.as<uint8_t>(), hdr, firstPiece ? hl : 0,
                              lastPiece && endMark, (uint8_t*)d_out + pos, out_cap - pos, &size, s))
       return r;
     pos += size;
     for (int i = 0; i < kStages; i++) stageSum[i] += c->stageMs[i];
     if (!(firstPiece && lastPiece)) {
       // every piece's block sizes, for sz4_last_block_sizes
-      const uint32_t nb = (uint32_t)c->plan.blocks.size();
+      const uint32_t nb = (uint32_t)c->pipe.plan.blocks.size();
       const size_t at = c->hostBytes.size();
       c->hostBytes.resize(at + nb);
-      if ((e = hipMemcpy(c->hostBytes.data() + at, c->blockBytes.p, nb * 4, hipMemcpyDeviceToHost)))
+      if ((e = hipMemcpy(c->hostBytes.data() + at, c->pipe.blockBytes.p, nb * 4, hipMemcpyDeviceToHost)))
         return c->fail(SZ4_E_DEVICE, "block sizes", e);
     }
   }
@@ -1445,7 +1482,7 @@ int64_t sz4_last_block_sizes(sz4_ctx* c, uint32_t* sizes, uint64_t max_blocks)
     return (int64_t)nb;
   }
   const uint64_t nb = std::min<uint64_t>(c->lastBlocks, max_blocks);
-  if (nb && hipMemcpy(sizes, c->blockBytes.p, nb * 4, hipMemcpyDeviceToHost) != hipSuccess) return SZ4_E_DEVICE;
+  if (nb && hipMemcpy(sizes, c->pipe.blockBytes.p, nb * 4, hipMemcpyDeviceToHost) != hipSuccess) return SZ4_E_DEVICE;
   for (uint64_t i = 0; i < nb; i++) sizes[i] &= 0x7FFFFFFFu;
   return (int64_t)nb;
 }
@@ -1720,6 +1757,145 @@ int sz4_dq_enqueue(sz4_dq* q, const void* const* d_src, const uint32_t* d_src_si
   return hipGetLastError() == hipSuccess ? SZ4_OK : SZ4_E_DEVICE;
 }
 
+// ---- compress queue: a ragged run planned, reserved and uploaded once, in a pipe of its own (held) ------------
+struct sz4_cq {
+  sz4_ctx* ctx;
+  uint32_t count = 0;        // caller items
+  uint32_t maxChain = 0;
+  bool planes = false;       // an item is wider than 1: the item table is BatchTyped, staged by k_batch_gather_planes
+  uint64_t bound = 0;        // sz4_batch_bound of the sizes
+  uint64_t stagedBytes = 0;  // the gather's extent: the items' strides and the pad
+  uint64_t longBitsBytes = 0;
+  Pipe pipe;
+  DevBuf map;                // per caller item: its block (CqTables::map)
+  PipeArgs args{};           // the launchers' view of `pipe`, but for the output address
+  explicit sz4_cq(sz4_ctx* c) : ctx(c), pipe(c->budget, true), map(c->budget, true) {}
+  void detach()
+  {
+    pipe.detach();
+    map.detach();
+  }
+};
+
+int sz4_cq_create(sz4_ctx* c, const uint32_t* sizes, const uint8_t* elem_sizes, uint32_t count, uint32_t max_chain, sz4_cq** q)
+{
+  if (q) *q = nullptr;
+  if (!c || !q || (count && !sizes)) return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
+  if (count < 1 || count > kBatchMaxBlocks) return c->fail(SZ4_E_ARG, "count is not 1 .. 32768");
+  if ((max_chain >= 1 && max_chain <= (uint32_t)kLazyMax) || max_chain > 65535)
+    return c->fail(SZ4_E_ARG, "a compress queue runs level 0 and max_chain 7 .. 65535 (levels 1 .. 6 read status words on the host)");
+  uint64_t staged = 0;
+  bool planes = false;
+  for (uint32_t i = 0; i < count; i++) {
+    if (sizes[i] > kBlockMax) return c->fail(SZ4_E_ARG, "item larger than 4 MiB");
+    const uint8_t e = elem_sizes ? elem_sizes[i] : 1;
+    if (e != 1 && e != 2 && e != 4 && e != 8) return c->fail(SZ4_E_ARG, "element width is not 1, 2, 4 or 8");
+    planes |= e > 1;
+    staged += batch_stride(sizes[i]);
+  }
+  if (staged > kBatchChunkDefault) return c->fail(SZ4_E_ARG, "the items stage more than 448 MiB");
+  c->begin_call();
+  DeviceGuard guard(c->device);
+  sz4_cq* d = nullptr;
+  try {
+    d = new sz4_cq(c);
+    d->count = count;
+    d->maxChain = max_chain;
+    d->planes = planes;
+    d->bound = sz4_batch_bound(sizes, count);
+    // the non-empty items are the plan's blocks, in caller order; an empty item maps to the block that follows it
+    std::vector<uint64_t> runSizes;
+    std::vector<uint32_t> map(count);
+    for (uint32_t i = 0; i < count; i++) {
+      map[i] = (uint32_t)runSizes.size() | (sizes[i] ? 0u : kCqEmpty);
+      if (sizes[i]) runSizes.push_back(sizes[i]);
+    }
+    const uint32_t nb = (uint32_t)runSizes.size();
+    Pipe& P = d->pipe;
+    d->stagedBytes = P.plan.build_ragged(runSizes) + kPad;
+    d->longBitsBytes = nb ? P.plan.blocks.back().end / 8 + 8 : 0;
+    // the item table with everything but the sources, which k_cq_items fills in on every enqueue
+    std::vector<BatchItem> items(planes ? 0 : nb);
+    std::vector<BatchTyped> typed(planes ? nb : 0);
+    for (uint32_t i = 0; i < count; i++) {
+      if (!sizes[i]) continue;
+      const uint32_t b = map[i];
+      if (planes) typed[b] = BatchTyped{0, P.plan.blocks[b].start, sizes[i], elem_sizes[i]};
+      else items[b] = BatchItem{0, P.plan.blocks[b].start, sizes[i]};
+    }
+    hipError_t e;
+    if ((e = P.reserve(d->stagedBytes)) || (e = P.staged.reserve(d->stagedBytes)) ||
+        (e = P.batchItems.reserve(nb * sizeof(BatchItem) + 64)) || (e = d->map.reserve(count * 4ull))) {
+      d->detach();
+      delete d;
+      return c->fail(SZ4_E_NOMEM, "compress queue scratch", e);
+    }
+    if ((e = P.upload_plan(nullptr)) ||
+        (nb && (e = hipMemcpyAsync(P.batchItems.p, planes ? (const void*)typed.data() : (const void*)items.data(),
+                                   nb * sizeof(BatchItem), hipMemcpyHostToDevice, nullptr))) ||
+        (e = hipMemcpyAsync(d->map.p, map.data(), count * 4ull, hipMemcpyHostToDevice, nullptr)) ||
+        (e = hipStreamSynchronize(nullptr))) {
+      d->detach();
+      delete d;
+      return c->fail(SZ4_E_DEVICE, "upload plan", e);
+    }
+    d->args = P.args(max_chain, P.staged.as<uint8_t>(), nullptr, 0);
+  } catch (const std::bad_alloc&) {
+    if (d) {
+      d->detach();
+      delete d;
+    }
+    return c->fail(SZ4_E_NOMEM, "host allocation");
+  }
+  *q = d;
+  return SZ4_OK;
+}
+
+void sz4_cq_destroy(sz4_cq* q)
+{
+  if (!q) return;
+  DeviceGuard guard(q->ctx->device);
+  q->detach();
+  delete q;
+}
+
+uint64_t sz4_cq_bound(const sz4_cq* q) { return q ? q->bound : 0; }
+
+// Kernel launches only: no allocation, no copy, no wait, and nothing of the context's call state is touched.
+// The launch sequence is run_pipeline's for independent blocks at level 0 and the parsed levels, where it reads
+// nothing back; what run_pipeline clears with memsets (and the ghost slot it uploads) k_cq_items and k_cq_zero
+// clear, because a captured memset did not replay reliably
+int sz4_cq_enqueue(sz4_cq* q, const void* const* d_src, void* d_out, uint64_t out_cap, uint64_t* d_block_ptrs,
+                   uint32_t* d_block_sizes, uint32_t* d_status, uint64_t* d_total, void* stream)
+{
+  if (!q || !d_src || !d_out || !d_block_ptrs || !d_block_sizes || !d_status) return SZ4_E_ARG;
+  if (out_cap < q->bound) return SZ4_E_CAPACITY;
+  DeviceGuard guard(q->ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  PipeArgs P = q->args;
+  P.out = (uint8_t*)d_out;
+  const uint32_t nb = P.nblocks;
+  const CqTables T{reinterpret_cast<const uint64_t*>(d_src), q->map.as<uint32_t>(), q->count, P.out, d_block_ptrs,
+                   d_block_sizes, d_status, d_total};
+  launch_cq_items(T, P, q->pipe.batchItems.p, q->planes, s);
+  if (nb) {
+    uint8_t* staged = q->pipe.staged.as<uint8_t>();
+    if (q->planes) launch_batch_gather_planes(q->pipe.batchItems.as<BatchTyped>(), nb, staged, q->stagedBytes, s);
+    else launch_batch_gather(q->pipe.batchItems.as<BatchItem>(), nb, staged, q->stagedBytes, s);
+    launch_runs(P, s);
+    if (q->maxChain > 0) {
+      launch_cq_zero(P.longBits, q->longBitsBytes, s);
+      launch_find(1, P, s);
+      launch_find(2, P, s);
+    }
+    launch_prep(P, s);
+    launch_parse(P, s);
+    launch_emit(P, s);
+  }
+  launch_cq_finish(T, P, s);
+  return hipGetLastError() == hipSuccess ? SZ4_OK : SZ4_E_DEVICE;
+}
+
 int sz4_lz4_stream(sz4_ctx* c, sz4_get_bytes get_bytes, sz4_send_bytes send_bytes, uint32_t max_chain, const void* dict,
                    uint64_t dict_len, int legacy, void* user)
 {
@@ -1781,10 +1957,10 @@ void sz4_debug_stop_after(sz4_ctx* c, int stop_after)
 static int debug_copy(sz4_ctx* c, bool choices, uint32_t* len, uint16_t* dist, uint64_t n)
 {
   if (!c || !len || !dist) return SZ4_E_ARG;
-  if (n * 4 > c->mlen.cap || n * 2 > c->mdist.cap) return SZ4_E_ARG;
-  const uint32_t* lens = choices ? c->sel() : c->mlen.as<uint32_t>();
+  if (n * 4 > c->pipe.mlen.cap || n * 2 > c->pipe.mdist.cap) return SZ4_E_ARG;
+  const uint32_t* lens = choices ? c->pipe.sel() : c->pipe.mlen.as<uint32_t>();
   if (hipMemcpy(len, lens, n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(dist, c->mdist.p, n * 2, hipMemcpyDeviceToHost) != hipSuccess)
+      hipMemcpy(dist, c->pipe.mdist.p, n * 2, hipMemcpyDeviceToHost) != hipSuccess)
     return SZ4_E_DEVICE;
   return SZ4_OK;
 }

@@ -108,7 +108,7 @@ constexpr uint32_t kLazyCap = 1400;
 constexpr uint32_t lazy_slots_per_walk() { return 2 * kLazyCap; }
 
 // The buffers of one pipeline run, as every compressor launcher takes them: the host driver fills one
-// PipeArgs per run (pipe_args in sz4_host.cpp) once all of the run's buffers are reserved.  Arrays "per
+// PipeArgs per run (Pipe::args in sz4_host.cpp) once all of the run's buffers are reserved.  Arrays "per
 // position" are indexed by the absolute staged position, like Block's fields.
 struct PipeArgs {
   const uint8_t* in;        // the staged input (padded: the kernels read 4-byte windows past the last block)
@@ -326,5 +326,30 @@ struct BatchMove {
   uint64_t src, dst, len;
 };
 void launch_batch_move(const BatchMove* moves, uint32_t n, const uint8_t* from, uint8_t* to, hipStream_t s);
+
+// compress queue (sz4_cq_enqueue): the caller's device tables, `count` entries each, around one ragged run whose
+// blocks are the non-empty items in caller order.  map[i] is the block of the first non-empty item at or after
+// item i (nblocks: there is none), with kCqEmpty set when item i itself is empty
+constexpr uint32_t kCqEmpty = 0x80000000u;
+struct CqTables {
+  const uint64_t* src;   // the items' device addresses (an empty item's entry is not read)
+  const uint32_t* map;
+  uint32_t count;
+  uint8_t* out;          // where the run writes its blocks
+  uint64_t* blockPtrs;   // results: every block's address in `out`, its bytes (size word included), kItem*
+  uint32_t* blockSizes;
+  uint32_t* status;
+  uint64_t* total;       // the bytes written to `out` (may be null)
+};
+// before the gather: the sources into the run's resident item table (BatchTyped when `typed`, else BatchItem;
+// start and elem stay as uploaded), and every item's first status.  A null source of a non-empty item gets
+// size 0 in the table -- the gather stages zeros for it, nothing is read -- and kItemArg.  Also clears P's
+// status word, longFlag, ghost interval count and (no blocks) body size, which a synchronous run memsets
+void launch_cq_items(const CqTables& T, const PipeArgs& P, void* items, bool typed, hipStream_t s);
+// zeroes [p, p + bytes rounded up to 16) with a kernel (p is 16-byte aligned)
+void launch_cq_zero(void* p, uint64_t bytes, hipStream_t s);
+// after the assembly: addresses and sizes from P.offsets / P.blockBytes; kItemInternal for every item, with
+// size 0 and a total of 0, when P's status word carries kStInvariant
+void launch_cq_finish(const CqTables& T, const PipeArgs& P, hipStream_t s);
 
 }  // namespace sz4
