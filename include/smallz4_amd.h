@@ -270,6 +270,34 @@ uint64_t sz4_cq_bound(const sz4_cq* q);
 int sz4_cq_enqueue(sz4_cq* q, const void* const* d_src, void* d_out, uint64_t out_cap, uint64_t* d_block_ptrs,
                    uint32_t* d_block_sizes, uint32_t* d_status, uint64_t* d_total, void* stream);
 
+/* ---- sized compress queue: the item sizes come from a device table at every enqueue ---------------------------
+ * As sz4_cq_create, but caps[i] is the LARGEST size item i may have at an enqueue (0 .. 4 MiB; an item of
+ * capacity 0 is always empty).  The limits are sz4_cq_create's, applied to the capacities, and
+ * sz4_cq_bound(q) == sz4_batch_bound(caps, count).  Every item keeps a fixed slot of the scratch, laid out for
+ * its capacity; sz4_cq_destroy serves both kinds of queue.  The SZ4_DP_SIZE tuning knob does not apply. */
+int sz4_cq_create_sized(sz4_ctx* ctx, const uint32_t* caps, const uint8_t* elem_sizes, uint32_t count,
+                        uint32_t max_chain, sz4_cq** q);
+
+/* As sz4_cq_enqueue, plus d_src_sizes: a DEVICE table of `count` sizes, read when the kernels run -- a captured
+ * enqueue replayed after the table was rewritten compresses the new sizes.  With n = d_src_sizes[i], item i gives
+ *   0 < n <= caps[i]   exactly the block sz4_compress_batch_typed_device writes for the n bytes at d_src[i] with
+ *                      width elem_sizes[i] (the reference's block of split(item[:n], width)); SZ4_ITEM_OK.
+ *                      A null d_src[i] is never dereferenced: n zeros are compressed, SZ4_ITEM_ARG
+ *   n == 0             no bytes: size 0 at the address where the next block starts; d_src[i] is not looked at;
+ *                      SZ4_ITEM_OK
+ *   n > caps[i]        as an empty item, the source is not read; SZ4_ITEM_CAPACITY
+ * Blocks lie back to back in caller order, d_total is their sum, and no store lands at or beyond
+ * d_out + sz4_cq_bound(q).  SZ4_ITEM_INTERNAL keeps its meaning.  Everything else said of sz4_cq_enqueue
+ * holds: kernel launches only (no memset, copy, wait or allocation), one chain on one stream, not a call on
+ * the context.  The launches and their grids are those of the capacities, whatever the sizes: an enqueue of
+ * small sizes costs the launch slots of the full capacities (a wavefront that finds its entry unused returns
+ * at once), plus one small kernel that re-derives the plan.
+ * sz4_cq_enqueue on a sized queue, sz4_cq_enqueue_sized on a queue of sz4_cq_create, and a null d_src_sizes
+ * return SZ4_E_ARG before any device work. */
+int sz4_cq_enqueue_sized(sz4_cq* q, const void* const* d_src, const uint32_t* d_src_sizes, void* d_out,
+                         uint64_t out_cap, uint64_t* d_block_ptrs, uint32_t* d_block_sizes, uint32_t* d_status,
+                         uint64_t* d_total, void* stream);
+
 /* Whole-stream compression with the exact semantics of
  * smallz4::lz4(getBytes, sendBytes, maxChainLength, dictionary, useLegacyFormat)
  * (reference smallz4.h:47-64): 4 MiB dependent blocks (8 MiB independent

@@ -19,6 +19,8 @@ plus the data-parallel entry point the GPU is built for:
         -> the batch decoders as an enqueue over device tables: no host synchronisation, graph-capturable
     Compressor().compress_queue(sizes, elems, max_chain_length) -> CompressQueue.enqueue(...) / tensor_tables(t)
         -> the typed batch compressor as an enqueue for a fixed set of item sizes, graph-capturable as well
+    Compressor().compress_queue_sized(capacities, elems, max_chain_length) -> SizedCompressQueue.enqueue(...)
+        -> the same with the item sizes read from a device table at every enqueue, up to fixed capacities
 
 All compression runs in the HIP library smallz4_amd/lib/libsmallz4_amd.so; there
 is no CPU fallback.
@@ -174,6 +176,8 @@ class CompressQueue:
     block_sizes are a DecodeQueue's src_ptrs and src_sizes.  Holds its scratch (about 50 bytes per staged byte)
     until close(); close it before its Compressor, and after every graph captured from it is gone."""
 
+    _create = "sz4_cq_create"
+
     def __init__(self, comp: "Compressor", sizes, elems=None, max_chain_length: int = MaxChainLength):
         self._comp = comp
         self._lib = comp._lib
@@ -190,7 +194,8 @@ class CompressQueue:
         if self.elems is not None:
             w = (ctypes.c_uint8 * max(self.count, 1))(*[x & 0xFF if 0 <= x < 256 else 0 for x in self.elems])
         h = ctypes.c_void_p()
-        comp._check(self._lib.sz4_cq_create(comp._h, z, w, self.count, int(max_chain_length), ctypes.byref(h)), "sz4_cq_create")
+        comp._check(getattr(self._lib, self._create)(comp._h, z, w, self.count, int(max_chain_length), ctypes.byref(h)),
+                    self._create)
         self._h = h
         self.bound = int(self._lib.sz4_cq_bound(h))
 
@@ -238,6 +243,53 @@ class CompressQueue:
             ptrs.append(at)
             at += n
         return torch.tensor(ptrs, dtype=torch.int64).to(dev)
+
+
+class SizedCompressQueue(CompressQueue):
+    """A CompressQueue whose item sizes are read from a device table at every enqueue (sz4_cq_create_sized /
+    sz4_cq_enqueue_sized): what is fixed here is every item's CAPACITY, the largest size it may have.  Item i
+    of an enqueue has src_sizes[i] bytes: 0 gives an empty item, more than capacities[i] an empty item with
+    status SZ4_ITEM_CAPACITY.  The scratch and the launches are those of the capacities, whatever the sizes.
+    close / __del__ as on CompressQueue."""
+
+    _create = "sz4_cq_create_sized"
+
+    def __init__(self, comp: "Compressor", capacities, elems=None, max_chain_length: int = MaxChainLength):
+        super().__init__(comp, capacities, elems, max_chain_length)
+        self.capacities = self.sizes
+        del self.sizes  # an enqueue's sizes are its src_sizes table
+
+    def enqueue(self, src_ptrs, src_sizes, out, block_ptrs, block_sizes, status, total=None, stream=None):
+        """As CompressQueue.enqueue, with src_sizes: an int32 device tensor of this enqueue's item sizes, read
+        when the stream gets there (see sz4_cq_enqueue_sized)."""
+        import torch
+        table = DecodeQueue._table
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.sz4_cq_enqueue_sized(
+            self._h, table(src_ptrs, torch.int64, self.count, "src_ptrs"), table(src_sizes, torch.int32, self.count, "src_sizes"),
+            table(out, torch.uint8, 0, "out"), out.numel(),
+            table(block_ptrs, torch.int64, self.count, "block_ptrs"), table(block_sizes, torch.int32, self.count, "block_sizes"),
+            table(status, torch.int32, self.count, "status"), None if total is None else table(total, torch.int64, 1, "total"),
+            ctypes.c_void_p(stream))
+        if rc != _native.SZ4_OK:
+            raise _native.NativeError(f"sz4_cq_enqueue_sized failed ({rc})")
+
+    def tensor_tables(self, t):
+        """(src_ptrs, src_sizes) for the contiguous device tensor `t` cut at the capacities in order
+        (sum(capacities) must be t's bytes): the int64 pointer table, and an int32 size table preset to the
+        capacities, which the caller -- or a kernel of its own -- rewrites between enqueues."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not t.is_contiguous() or t.device != dev:
+            raise TypeError("t must be a contiguous tensor on the queue's device")
+        if t.numel() * t.element_size() != sum(self.capacities):
+            raise ValueError("the queue's capacities do not cover the tensor")
+        ptrs, at = [], t.data_ptr()
+        for n in self.capacities:
+            ptrs.append(at)
+            at += n
+        return torch.tensor(ptrs, dtype=torch.int64).to(dev), torch.tensor(self.capacities, dtype=torch.int32).to(dev)
 
 
 class Compressor:
@@ -603,6 +655,11 @@ class Compressor:
         at this level (0 or 7 .. 65535) (sz4_cq_create); its scratch counts as this context's until the queue
         is closed."""
         return CompressQueue(self, sizes, elems, max_chain_length)
+
+    def compress_queue_sized(self, capacities, elems=None, max_chain_length: int = MaxChainLength) -> "SizedCompressQueue":
+        """An enqueue-only batch compressor whose item sizes come from a device table at every enqueue, each up
+        to its capacity (sz4_cq_create_sized); otherwise as compress_queue."""
+        return SizedCompressQueue(self, capacities, elems, max_chain_length)
 
     def last_merge_ms(self) -> float:
         """Device time of the last unlz4_batch_typed_device call's merge kernel (with set_timing on)."""

@@ -65,6 +65,8 @@ SIGNATURES = {
     "sz4_cq_destroy": (None, [_vp]),
     "sz4_cq_bound": (_u64, [_vp]),
     "sz4_cq_enqueue": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "sz4_cq_create_sized": (_i32, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(ctypes.c_uint8), _u32, _u32, ctypes.POINTER(_vp)]),
+    "sz4_cq_enqueue_sized": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "sz4_lz4": (_i32, [_vp, _vp, _u64, _u32, _vp, _u64, _i32, _vp, _u64, ctypes.POINTER(_u64)]),
     "sz4_lz4_bound": (_u64, [_u64, _i32]),
     "sz4_lz4_stream": (_i32, [_vp, GET_BYTES, SEND_BYTES, _u32, _vp, _u64, _i32, _vp]),

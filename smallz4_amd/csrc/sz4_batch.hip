@@ -8,9 +8,12 @@
 // All are copies, bound by memory: 16-byte accesses on the aligned side, work cut by bytes.
 //   k_cq_items, k_cq_finish  the compress queue's ends (sz4_cq_enqueue): the caller's device pointer table
 //                   into the gather's item table, and the run's offsets and sizes out to the caller's tables
+//   k_cq_plan       a sized queue's first kernel (sz4_cq_enqueue_sized): k_cq_items' job, and every slot's plan
+//                   entries rewritten for the sizes in the caller's device table (sz4_slot_plan.h)
 #include <hip/hip_runtime.h>
 
 #include "sz4_internal.h"
+#include "sz4_slot_plan.h"
 
 namespace sz4 {
 namespace {
@@ -368,6 +371,50 @@ __global__ __launch_bounds__(256) void k_cq_items(const uint64_t* __restrict__ s
   status[i] = st;
 }
 
+// A sized queue's k_cq_items: one wavefront per slot (caller item i is block i).  With n = srcSizes[i]:
+//   n > cap            the slot is empty at this enqueue (kItemCapacity); neither the source entry nor the
+//                      source is read
+//   n == 0             the slot is empty (kItemOk); the source entry is not read
+//   null source        the gather's size is 0, so the slot's n staged bytes are zeros (kItemArg)
+// Lane 0 writes the gather's item entry (source and size; start and width stay as uploaded), the slot's Block
+// and the statuses; the lanes share the slot's Segment and DpSeg entries, which sz4_slot_plan.h derives from
+// (slot, n) -- inert where n needs fewer than the capacity reserved.  Walk entries never change.  A 4 MiB slot
+// has 64 + 512 entries.  It clears what k_cq_items clears.
+template <typename Item>
+__global__ __launch_bounds__(256) void k_cq_plan(const uint64_t* __restrict__ src, const uint32_t* __restrict__ srcSizes,
+                                                 uint32_t count, const Slot* __restrict__ slots, Block* __restrict__ blocks,
+                                                 Segment* __restrict__ segs, DpSeg* __restrict__ dp, Item* __restrict__ items,
+                                                 uint32_t* __restrict__ status, int* __restrict__ pipeStatus,
+                                                 uint32_t* __restrict__ longFlag, uint32_t* __restrict__ ivCount)
+{
+  const uint32_t lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *pipeStatus = 0;
+    ivCount[count] = 0;
+  }
+  if (i >= count) return;
+  const Slot s = slots[i];
+  const uint32_t want = srcSizes[i];
+  uint32_t st = kItemOk, n = want;
+  uint64_t p = 0;
+  if (want > s.cap) {
+    st = kItemCapacity;
+    n = 0;
+  } else if (want) {
+    p = src[i];
+    if (!p) st = kItemArg;
+  }
+  if (lane == 0) {
+    items[i].src = p;
+    items[i].size = p ? (decltype(items[i].size))n : 0;
+    blocks[i] = slot_block(s, n);
+    longFlag[i] = 0;
+    status[i] = st;
+  }
+  for (uint32_t j = lane; j < s.segCount; j += 64) segs[s.segFirst + j] = slot_segment(s, i, j, n);
+  for (uint32_t j = lane; j < s.dpCount; j += 64) dp[s.dpFirst + j] = slot_dp(i, j, n);
+}
+
 // zeroes `words` 16-byte words at p (the pass-2 marker bits, which the finders OR into)
 __global__ __launch_bounds__(256) void k_cq_zero(uint4* __restrict__ p, uint64_t words)
 {
@@ -388,7 +435,7 @@ __global__ __launch_bounds__(256) void k_cq_finish(const uint32_t* __restrict__ 
 {
   const bool bad = (*pipeStatus & kStInvariant) != 0;
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < count; i += gridDim.x * 256) {
-    const uint32_t m = map[i], b = m & ~kCqEmpty;
+    const uint32_t m = map ? map[i] : i, b = m & ~kCqEmpty;
     blockPtrs[i] = reinterpret_cast<uint64_t>(out) + (bad ? 0 : offsets[b]);
     blockSizes[i] = bad || (m & kCqEmpty) ? 0u : blockBytes[b] & 0x7FFFFFFFu;
     if (bad) status[i] = kItemInternal;
@@ -407,6 +454,22 @@ void launch_cq_items(const CqTables& T, const PipeArgs& P, void* items, bool typ
   else
     hipLaunchKernelGGL(k_cq_items<BatchItem>, grid, block, 0, s, T.src, T.map, T.count, P.nblocks, P.blocks,
                        static_cast<BatchItem*>(items), T.status, P.status, P.longFlag, P.ivCount, P.offsets);
+}
+
+void launch_cq_plan(const CqTables& T, const uint32_t* srcSizes, const Slot* slots, const PipeArgs& P, void* items, bool typed,
+                    hipStream_t s)
+{
+  // the plan tables are the queue's own (held) buffers: PipeArgs names them const for the pipeline's kernels
+  Block* blocks = const_cast<Block*>(P.blocks);
+  Segment* segs = const_cast<Segment*>(P.segs);
+  DpSeg* dp = const_cast<DpSeg*>(P.dpSegs);
+  const dim3 grid((T.count + 3) / 4), block(256);
+  if (typed)
+    hipLaunchKernelGGL(k_cq_plan<BatchTyped>, grid, block, 0, s, T.src, srcSizes, T.count, slots, blocks, segs, dp,
+                       static_cast<BatchTyped*>(items), T.status, P.status, P.longFlag, P.ivCount);
+  else
+    hipLaunchKernelGGL(k_cq_plan<BatchItem>, grid, block, 0, s, T.src, srcSizes, T.count, slots, blocks, segs, dp,
+                       static_cast<BatchItem*>(items), T.status, P.status, P.longFlag, P.ivCount);
 }
 
 void launch_cq_zero(void* p, uint64_t bytes, hipStream_t s)

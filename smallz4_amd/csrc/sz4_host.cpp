@@ -131,7 +131,9 @@ hipError_t Pipe::reserve(uint64_t stagedBytes)
       (e = offsets.reserve((nb + 1) * 8 + 64)) ||
       (e = status.reserve(64)) ||
       (e = dpSegs.reserve(plan.dp.size() * sizeof(DpSeg) + 64)) ||
-      (e = reach.reserve(stagedBytes * 4 + 64)) ||
+      // (after the parse the token walk's records live here: a uint4 per walk sub-segment and a uint2 per block,
+      // which outgrow the positions only where blocks stage nothing -- a sized queue's slots of capacity 0)
+      (e = reach.reserve(std::max<uint64_t>(stagedBytes * 4, plan.walk.size() * sizeof(uint4) + nb * sizeof(uint2)) + 64)) ||
       (e = segState.reserve(plan.dp.size() * sizeof(uint4) + 64)) ||
       (e = dpRec.reserve(plan.dp.size() * sizeof(uint4) + 64)) ||
       (e = walkSegs.reserve(plan.walk.size() * sizeof(uint2) + 64)) ||
@@ -1763,21 +1765,26 @@ struct sz4_cq {
   uint32_t count = 0;        // caller items
   uint32_t maxChain = 0;
   bool planes = false;       // an item is wider than 1: the item table is BatchTyped, staged by k_batch_gather_planes
+  bool sized = false;        // sz4_cq_create_sized: the sizes are capacities, every item has a slot (block i is item i)
   uint64_t bound = 0;        // sz4_batch_bound of the sizes
   uint64_t stagedBytes = 0;  // the gather's extent: the items' strides and the pad
   uint64_t longBitsBytes = 0;
   Pipe pipe;
-  DevBuf map;                // per caller item: its block (CqTables::map)
+  DevBuf map;                // per caller item: its block (CqTables::map); a sized queue has none
+  DevBuf slots;              // a sized queue's Slot table (sz4_slot_plan.h), read by k_cq_plan
   PipeArgs args{};           // the launchers' view of `pipe`, but for the output address
-  explicit sz4_cq(sz4_ctx* c) : ctx(c), pipe(c->budget, true), map(c->budget, true) {}
+  explicit sz4_cq(sz4_ctx* c) : ctx(c), pipe(c->budget, true), map(c->budget, true), slots(c->budget, true) {}
   void detach()
   {
     pipe.detach();
     map.detach();
+    slots.detach();
   }
 };
 
-int sz4_cq_create(sz4_ctx* c, const uint32_t* sizes, const uint8_t* elem_sizes, uint32_t count, uint32_t max_chain, sz4_cq** q)
+// both kinds of queue: `sizes` are the items' sizes, or (sized) their capacities
+static int cq_create(sz4_ctx* c, const uint32_t* sizes, const uint8_t* elem_sizes, uint32_t count, uint32_t max_chain,
+                     bool sized, sz4_cq** q)
 {
   if (q) *q = nullptr;
   if (!c || !q || (count && !sizes)) return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
@@ -1802,30 +1809,38 @@ int sz4_cq_create(sz4_ctx* c, const uint32_t* sizes, const uint8_t* elem_sizes, 
     d->count = count;
     d->maxChain = max_chain;
     d->planes = planes;
+    d->sized = sized;
     d->bound = sz4_batch_bound(sizes, count);
     // the non-empty items are the plan's blocks, in caller order; an empty item maps to the block that follows it
+    // (a sized queue: every item is a block, in its slot, whatever its capacity)
     std::vector<uint64_t> runSizes;
     std::vector<uint32_t> map(count);
     for (uint32_t i = 0; i < count; i++) {
-      map[i] = (uint32_t)runSizes.size() | (sizes[i] ? 0u : kCqEmpty);
-      if (sizes[i]) runSizes.push_back(sizes[i]);
+      map[i] = sized ? i : (uint32_t)runSizes.size() | (sizes[i] ? 0u : kCqEmpty);
+      if (sizes[i] && !sized) runSizes.push_back(sizes[i]);
     }
-    const uint32_t nb = (uint32_t)runSizes.size();
+    const uint32_t nb = sized ? count : (uint32_t)runSizes.size();
     Pipe& P = d->pipe;
-    d->stagedBytes = P.plan.build_ragged(runSizes) + kPad;
+    if (sized) {
+      d->stagedBytes = P.plan.build_slots(std::vector<uint32_t>(sizes, sizes + count)) + kPad;
+      for (uint32_t i = 0; i < count; i++) P.plan.slots[i].elem = elem_sizes ? elem_sizes[i] : 1;
+    } else {
+      d->stagedBytes = P.plan.build_ragged(runSizes) + kPad;
+    }
     d->longBitsBytes = nb ? P.plan.blocks.back().end / 8 + 8 : 0;
     // the item table with everything but the sources, which k_cq_items fills in on every enqueue
     std::vector<BatchItem> items(planes ? 0 : nb);
     std::vector<BatchTyped> typed(planes ? nb : 0);
     for (uint32_t i = 0; i < count; i++) {
-      if (!sizes[i]) continue;
+      if (!sizes[i] && !sized) continue;
       const uint32_t b = map[i];
       if (planes) typed[b] = BatchTyped{0, P.plan.blocks[b].start, sizes[i], elem_sizes[i]};
       else items[b] = BatchItem{0, P.plan.blocks[b].start, sizes[i]};
     }
     hipError_t e;
     if ((e = P.reserve(d->stagedBytes)) || (e = P.staged.reserve(d->stagedBytes)) ||
-        (e = P.batchItems.reserve(nb * sizeof(BatchItem) + 64)) || (e = d->map.reserve(count * 4ull))) {
+        (e = P.batchItems.reserve(nb * sizeof(BatchItem) + 64)) || (!sized && (e = d->map.reserve(count * 4ull))) ||
+        (sized && (e = d->slots.reserve(count * sizeof(Slot))))) {
       d->detach();
       delete d;
       return c->fail(SZ4_E_NOMEM, "compress queue scratch", e);
@@ -1833,7 +1848,8 @@ int sz4_cq_create(sz4_ctx* c, const uint32_t* sizes, const uint8_t* elem_sizes, 
     if ((e = P.upload_plan(nullptr)) ||
         (nb && (e = hipMemcpyAsync(P.batchItems.p, planes ? (const void*)typed.data() : (const void*)items.data(),
                                    nb * sizeof(BatchItem), hipMemcpyHostToDevice, nullptr))) ||
-        (e = hipMemcpyAsync(d->map.p, map.data(), count * 4ull, hipMemcpyHostToDevice, nullptr)) ||
+        (!sized && (e = hipMemcpyAsync(d->map.p, map.data(), count * 4ull, hipMemcpyHostToDevice, nullptr))) ||
+        (sized && (e = hipMemcpyAsync(d->slots.p, P.plan.slots.data(), count * sizeof(Slot), hipMemcpyHostToDevice, nullptr))) ||
         (e = hipStreamSynchronize(nullptr))) {
       d->detach();
       delete d;
@@ -1851,6 +1867,17 @@ int sz4_cq_create(sz4_ctx* c, const uint32_t* sizes, const uint8_t* elem_sizes, 
   return SZ4_OK;
 }
 
+int sz4_cq_create(sz4_ctx* c, const uint32_t* sizes, const uint8_t* elem_sizes, uint32_t count, uint32_t max_chain, sz4_cq** q)
+{
+  return cq_create(c, sizes, elem_sizes, count, max_chain, false, q);
+}
+
+int sz4_cq_create_sized(sz4_ctx* c, const uint32_t* caps, const uint8_t* elem_sizes, uint32_t count, uint32_t max_chain,
+                        sz4_cq** q)
+{
+  return cq_create(c, caps, elem_sizes, count, max_chain, true, q);
+}
+
 void sz4_cq_destroy(sz4_cq* q)
 {
   if (!q) return;
@@ -1864,20 +1891,23 @@ uint64_t sz4_cq_bound(const sz4_cq* q) { return q ? q->bound : 0; }
 // Kernel launches only: no allocation, no copy, no wait, and nothing of the context's call state is touched.
 // The launch sequence is run_pipeline's for independent blocks at level 0 and the parsed levels, where it reads
 // nothing back; what run_pipeline clears with memsets (and the ghost slot it uploads) k_cq_items and k_cq_zero
-// clear, because a captured memset did not replay reliably
-int sz4_cq_enqueue(sz4_cq* q, const void* const* d_src, void* d_out, uint64_t out_cap, uint64_t* d_block_ptrs,
-                   uint32_t* d_block_sizes, uint32_t* d_status, uint64_t* d_total, void* stream)
+// clear, because a captured memset did not replay reliably.  A sized queue (d_src_sizes) starts with k_cq_plan
+// in k_cq_items' place; the grids that follow are the capacity plan's, whatever the sizes
+static int cq_enqueue(sz4_cq* q, const void* const* d_src, const uint32_t* d_src_sizes, void* d_out, uint64_t out_cap,
+                      uint64_t* d_block_ptrs, uint32_t* d_block_sizes, uint32_t* d_status, uint64_t* d_total, void* stream)
 {
-  if (!q || !d_src || !d_out || !d_block_ptrs || !d_block_sizes || !d_status) return SZ4_E_ARG;
+  if (!q || !d_src || !d_out || !d_block_ptrs || !d_block_sizes || !d_status || q->sized != (d_src_sizes != nullptr))
+    return SZ4_E_ARG;
   if (out_cap < q->bound) return SZ4_E_CAPACITY;
   DeviceGuard guard(q->ctx->device);
   hipStream_t s = (hipStream_t)stream;
   PipeArgs P = q->args;
   P.out = (uint8_t*)d_out;
   const uint32_t nb = P.nblocks;
-  const CqTables T{reinterpret_cast<const uint64_t*>(d_src), q->map.as<uint32_t>(), q->count, P.out, d_block_ptrs,
-                   d_block_sizes, d_status, d_total};
-  launch_cq_items(T, P, q->pipe.batchItems.p, q->planes, s);
+  const CqTables T{reinterpret_cast<const uint64_t*>(d_src), q->sized ? nullptr : q->map.as<uint32_t>(), q->count, P.out,
+                   d_block_ptrs, d_block_sizes, d_status, d_total};
+  if (q->sized) launch_cq_plan(T, d_src_sizes, q->slots.as<Slot>(), P, q->pipe.batchItems.p, q->planes, s);
+  else launch_cq_items(T, P, q->pipe.batchItems.p, q->planes, s);
   if (nb) {
     uint8_t* staged = q->pipe.staged.as<uint8_t>();
     if (q->planes) launch_batch_gather_planes(q->pipe.batchItems.as<BatchTyped>(), nb, staged, q->stagedBytes, s);
@@ -1894,6 +1924,20 @@ int sz4_cq_enqueue(sz4_cq* q, const void* const* d_src, void* d_out, uint64_t ou
   }
   launch_cq_finish(T, P, s);
   return hipGetLastError() == hipSuccess ? SZ4_OK : SZ4_E_DEVICE;
+}
+
+int sz4_cq_enqueue(sz4_cq* q, const void* const* d_src, void* d_out, uint64_t out_cap, uint64_t* d_block_ptrs,
+                   uint32_t* d_block_sizes, uint32_t* d_status, uint64_t* d_total, void* stream)
+{
+  return cq_enqueue(q, d_src, nullptr, d_out, out_cap, d_block_ptrs, d_block_sizes, d_status, d_total, stream);
+}
+
+int sz4_cq_enqueue_sized(sz4_cq* q, const void* const* d_src, const uint32_t* d_src_sizes, void* d_out, uint64_t out_cap,
+                         uint64_t* d_block_ptrs, uint32_t* d_block_sizes, uint32_t* d_status, uint64_t* d_total,
+                         void* stream)
+{
+  if (!d_src_sizes) return SZ4_E_ARG;  // (cq_enqueue would take it for the fixed queue's call)
+  return cq_enqueue(q, d_src, d_src_sizes, d_out, out_cap, d_block_ptrs, d_block_sizes, d_status, d_total, stream);
 }
 
 int sz4_lz4_stream(sz4_ctx* c, sz4_get_bytes get_bytes, sz4_send_bytes send_bytes, uint32_t max_chain, const void* dict,

@@ -333,7 +333,7 @@ void launch_batch_move(const BatchMove* moves, uint32_t n, const uint8_t* from, 
 constexpr uint32_t kCqEmpty = 0x80000000u;
 struct CqTables {
   const uint64_t* src;   // the items' device addresses (an empty item's entry is not read)
-  const uint32_t* map;
+  const uint32_t* map;   // null in a sized queue: item i is block i
   uint32_t count;
   uint8_t* out;          // where the run writes its blocks
   uint64_t* blockPtrs;   // results: every block's address in `out`, its bytes (size word included), kItem*
@@ -346,6 +346,13 @@ struct CqTables {
 // size 0 in the table -- the gather stages zeros for it, nothing is read -- and kItemArg.  Also clears P's
 // status word, longFlag, ghost interval count and (no blocks) body size, which a synchronous run memsets
 void launch_cq_items(const CqTables& T, const PipeArgs& P, void* items, bool typed, hipStream_t s);
+// a sized queue's launch_cq_items (sz4_cq_enqueue_sized; T.map is null, P.nblocks == T.count): srcSizes is the
+// caller's DEVICE table of this enqueue's sizes, `slots` the queue's resident Slot table (sz4_slot_plan.h).
+// Besides launch_cq_items' work it rewrites P.blocks, P.segs and P.dpSegs for those sizes, and decides
+// kItemCapacity for a size above its slot's capacity
+struct Slot;
+void launch_cq_plan(const CqTables& T, const uint32_t* srcSizes, const Slot* slots, const PipeArgs& P, void* items, bool typed,
+                    hipStream_t s);
 // zeroes [p, p + bytes rounded up to 16) with a kernel (p is 16-byte aligned)
 void launch_cq_zero(void* p, uint64_t bytes, hipStream_t s);
 // after the assembly: addresses and sizes from P.offsets / P.blockBytes; kItemInternal for every item, with

@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void k_runs(const uint8_t* __restrict__ in, co
   __shared__ uint64_t s_edge;
   if (tid == 0) s_count = 0;
   const uint64_t n = B.end - B.start;
-  if (n < (uint64_t)kSameLetter + kTailNoMatch + 2) {
+  if (n < (uint64_t)kSameLetter + kTailNoMatch + 2) {  // (a sized queue's empty slot, n == 0, leaves here too)
     if (tid == 0) ivCount[blockIdx.x] = 0;
     return;
   }
@@ -872,6 +872,7 @@ __device__ __forceinline__ void find_sorted_body(const uint8_t* __restrict__ in,
   // the 8 XCDs, MI355X_MICROARCH.md "Workgroup dispatch"), so the runs stay in that XCD's L2
   const uint32_t segIdx = blockIdx.x;
   const Segment S = segs[segIdx];
+  if (S.s0 == S.s1) return;  // an inert entry of a sized queue's slot (sz4_slot_plan.h); uniform
   const Block B = blocks[S.block];
   const uint32_t tid = threadIdx.x, lane = tid & 63;
   const uint32_t waveId = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
@@ -1693,8 +1694,9 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
 {
   extern __shared__ __attribute__((aligned(16))) uint32_t win[];
   __shared__ uint32_t s_next;
-  if (!segLong[blockIdx.x]) return;  // pass 1 left nothing here (uniform)
   const Segment S = segs[blockIdx.x];
+  if (S.s0 == S.s1) return;  // an inert entry of a sized queue's slot (sz4_slot_plan.h): pass 1 wrote no segLong; uniform
+  if (!segLong[blockIdx.x]) return;  // pass 1 left nothing here (uniform)
   const Block B = blocks[S.block];
   const uint32_t tid = threadIdx.x, lane = tid & 63, row = lane >> 4, li = lane & 15;
   const void* compact = compactAll + S.elemOff;
@@ -2074,6 +2076,7 @@ __device__ __forceinline__ void find_long9_body(const uint8_t* __restrict__ in, 
   __shared__ uint32_t nEx;
   __shared__ uint32_t s_scan[kFindThreads / 64];
   const Segment S = segs[blockIdx.x];
+  if (S.s0 == S.s1) return;  // an inert entry of a sized queue's slot (sz4_slot_plan.h); uniform
   const Block B = blocks[S.block];
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const void* compact = compactAll + S.elemOff;
@@ -2684,6 +2687,7 @@ __global__ __launch_bounds__(kFindThreads) __attribute__((amdgpu_waves_per_eu(8)
   __shared__ uint32_t s_hasHead[kFindThreads / 64], s_outValid[kFindThreads / 64];
   __shared__ uint64_t s_outKey[kFindThreads / 64];
   const Segment S = segs[blockIdx.x];
+  if (S.s0 == S.s1) return;  // an inert entry of a sized queue's slot (sz4_slot_plan.h); uniform
   const Block B = blocks[S.block];
   if (B.cut != kNone || B.low != B.start)
     return;  // uniform over the workgroup (the resolve launch returns here for every segment of the block)
@@ -4038,7 +4042,7 @@ __global__ __launch_bounds__(64) void k_prep(const uint8_t* __restrict__ in, con
   uint32_t* L = mlen + B.start;
   uint16_t* D = mdist + B.start;
   uint32_t* S = sel + B.start;
-  if (maxChain == 0) return;
+  if (maxChain == 0 || n == 0) return;  // n == 0: a sized queue's slot that is empty at this enqueue
   const uint64_t lastSearch = n >= (uint64_t)kTailNoMatch ? n - kTailNoMatch : 0;  // inclusive, relative
 
   // positions the reference never searched keep length 0 (it leaves them default-constructed)
@@ -4646,6 +4650,7 @@ __device__ __forceinline__ void dp_spec_body(const Block* __restrict__ blocks,
   uint32_t* ring = rings[wave];
   const DpSeg G = dpSegs[segIdx];
   const Block B = blocks[G.block];
+  if (G.k >= B.dpCount) return;  // an inert entry of a sized queue's slot (sz4_slot_plan.h); uniform per wave
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t base = B.start;
   const uint32_t* L = mlen + base;
@@ -5130,6 +5135,7 @@ const Block* __restrict__ blocks, const DpSeg* __restrict__ dpSegs,
   }
   const Block B = blocks[bIdx];
   if (B.dpCount <= 1) return;
+  if (kPar && kFirst >= B.dpCount) return;  // an inert entry of a sized queue's slot (sz4_slot_plan.h)
   const uint32_t lane = threadIdx.x;
   SZ4_D7(
   // k_dp_fix<false> per block: serial positions, closed-form chunks, literal chunks, segments walked
@@ -5614,6 +5620,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_walk(const Block* __restric
   const uint32_t lane = threadIdx.x & 63;
   const uint2 ws = walkSegs[idx];
   const Block B = blocks[ws.x];
+  if (ws.y >= B.walkCount) return;  // an inert entry of a sized queue's slot (sz4_slot_plan.h); uniform per wave
   const uint32_t n = (uint32_t)(B.end - B.start);
   const uint32_t* L = chosen + B.start;
   uint32_t* slots = slotsAll + (uint64_t)idx * (2 * kWalkCap) + kWalkCap;
@@ -5746,6 +5753,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_walk_fix_spec(const Block* 
   if (ws.y == 0) return;
   const uint32_t lane = threadIdx.x & 63;
   const Block B = blocks[ws.x];
+  if (ws.y >= B.walkCount) return;  // an inert entry of a sized queue's slot (sz4_slot_plan.h); uniform per wave
   const uint32_t n = (uint32_t)(B.end - B.start);
   const uint32_t a = ws.y * kWalkSeg, aNext = a + kWalkSeg < n ? a + kWalkSeg : n;
   uint32_t* slots = slotsAll + (uint64_t)idx * (2 * kWalkCap);
@@ -5766,7 +5774,7 @@ __global__ __launch_bounds__(64) void k_walk_fix_commit(const Block* __restrict_
 {
   __shared__ uint32_t fix[kWalkCap];
   const Block B = blocks[blockIdx.x];
-  if (B.walkCount < 2) return;
+  if (B.walkCount < 2) return;  // (also a sized queue's slot that is empty at this enqueue: no sub-segment)
   const uint32_t lane = threadIdx.x;
   const uint32_t n = (uint32_t)(B.end - B.start);
   const uint32_t* L = chosen + B.start;
@@ -5878,6 +5886,7 @@ __global__ __launch_bounds__(kAsmThreads) void k_seg_scan(const Block* __restric
 {
   __shared__ uint32_t s_sum[kAsmThreads / 64], s_max[kAsmThreads / 64];
   const Block B = blocks[blockIdx.x];
+  if (B.start == B.end) return;  // a sized queue's slot that is empty at this enqueue; uniform
   const uint32_t* L = chosen + B.start;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   uint32_t carrySum = 0, carryMax = 0;
@@ -5930,6 +5939,7 @@ __global__ __launch_bounds__(64 * kSegWaves) void k_seg_tokens(const Block* __re
   const uint32_t lane = threadIdx.x & 63;
   const uint2 ws = walkSegs[idx];
   const Block B = blocks[ws.x];
+  if (ws.y >= B.walkCount) return;  // an inert entry of a sized queue's slot (sz4_slot_plan.h); uniform per wave
   const uint32_t n = (uint32_t)(B.end - B.start);
   const uint32_t* L = chosen + B.start;
   const uint16_t* D = mdist + B.start;
@@ -5985,6 +5995,12 @@ __global__ __launch_bounds__(kAsmThreads) void k_block_bytes(const Block* __rest
   const Block B = blocks[blockIdx.x];
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint64_t n = B.end - B.start;
+  if (n == 0) {
+    // a sized queue's slot that is empty at this enqueue: no block at all, not even a size word (k_scan and
+    // k_cq_finish read both words of every block); uniform
+    if (tid == 0) ntokOut[blockIdx.x] = 0u, blockBytes[blockIdx.x] = 0u;
+    return;
+  }
   const bool stored = maxChain == 0;
   const bool legacy = (B.flags & kBlkLegacy) != 0;
   uint64_t enc = 0;
@@ -6035,6 +6051,7 @@ __global__ __launch_bounds__(64 * kSegWaves) void k_write_seg(const uint8_t* __r
   const uint32_t lane = threadIdx.x & 63;
   const uint2 ws = walkSegs[idx];
   const Block B = blocks[ws.x];
+  if (ws.y >= B.walkCount) return;  // an inert entry of a sized queue's slot (sz4_slot_plan.h); uniform per wave
   const uint64_t n = B.end - B.start;
   const uint32_t bb = blockBytes[ws.x];
   const bool raw = (bb & 0x80000000u) != 0;

@@ -25,6 +25,7 @@ bool Plan::begin(const PlanKey& k)
   if (k == key) return false;
   key = PlanKey{};
   blocks.clear();
+  slots.clear();
   return true;
 }
 
@@ -163,6 +164,51 @@ uint64_t Plan::build_ragged(const std::vector<uint64_t>& sizes)
     at += batch_stride(n);
   }
   finish_plan(k);
+  return at;
+}
+
+uint64_t Plan::build_slots(const std::vector<uint32_t>& caps)
+{
+  const PlanKey k{PlanKey::kRagged};
+  begin(k);
+  version++;
+  segs.clear();
+  dp.clear();
+  walk.clear();
+  elemTotal = rankTotal = tokTotal = 0;
+  maxDpCount = 1;
+  ldsWindow = true;
+  uint64_t at = 0;
+  for (uint32_t cap : caps) {
+    const uint32_t bi = (uint32_t)blocks.size();
+    Slot s{};
+    s.start = at;
+    s.tokOff = tokTotal;
+    s.elemOff = elemTotal;
+    s.rankOff = rankTotal;
+    s.cap = cap;
+    s.elem = 1;
+    s.segFirst = (uint32_t)segs.size();
+    s.segCount = slot_seg_count(cap);
+    s.dpFirst = (uint32_t)dp.size();
+    s.dpCount = slot_dp_reserve(cap);
+    s.walkFirst = (uint32_t)walk.size();
+    s.walkCount = slot_walk_count(cap);
+    slots.push_back(s);
+    blocks.push_back(slot_block(s, cap));
+    for (uint32_t j = 0; j < s.segCount; j++) segs.push_back(slot_segment(s, bi, j, cap));
+    for (uint32_t j = 0; j < s.dpCount; j++) dp.push_back(slot_dp(bi, j, cap));
+    for (uint32_t j = 0; j < s.walkCount; j++) walk.push_back(make_uint2(bi, j));
+    tokTotal += token_capacity(cap);
+    elemTotal += slot_elem_reserve(cap);
+    rankTotal += slot_rank_reserve(cap);
+    maxDpCount = std::max(maxDpCount, s.dpCount);
+    // the widest window of any size is the capacity's: block end - w0 grows with the size
+    for (uint32_t j = 0; j < s.segCount; j++)
+      if ((blocks[bi].end - segs[s.segFirst + j].w0 + 8 + 3) / 4 * 4 > find_lds_bytes()) ldsWindow = false;
+    at += batch_stride(cap);
+  }
+  key = k;
   return at;
 }
 

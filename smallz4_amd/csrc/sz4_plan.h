@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "sz4_internal.h"
+#include "sz4_slot_plan.h"
 
 namespace sz4 {
 
@@ -44,6 +45,7 @@ struct Plan {
   std::vector<Segment> segs;  // the match search's segments
   std::vector<DpSeg> dp;      // the parse's segments
   std::vector<uint2> walk;    // the token walk's sub-segments (block, index in the block)
+  std::vector<Slot> slots;    // build_slots alone: the slot of every block (empty for every other plan)
   uint64_t elemTotal = 0, rankTotal = 0, tokTotal = 0;
   bool ldsWindow = false;     // every segment's window fits the finders' LDS
   uint32_t maxDpCount = 1;    // the largest dpCount of the blocks (at least 1)
@@ -69,6 +71,12 @@ struct Plan {
   // one independent block per item (sizes > 0), at ascending multiples of kBatchAlign; returns the end of the
   // last item's stride (the bytes the gather stages, before the pad)
   uint64_t build_ragged(const std::vector<uint64_t>& sizes);
+  // a sized compress queue's plan (sz4_slot_plan.h): one slot per capacity (0 allowed), empty ones included, at
+  // the running sum of the capacities' strides.  Every table holds what the slot reserves -- the largest count
+  // any size <= cap needs -- with the entries of size == cap, the rest inert; the totals, maxDpCount and
+  // ldsWindow follow from the reserved counts and the capacities, so the scratch laid out for this plan holds
+  // every plan of smaller sizes.  Slot::elem is left 1.  Returns the end of the last slot's stride
+  uint64_t build_slots(const std::vector<uint32_t>& caps);
 
  private:
   bool begin(const PlanKey& k);
