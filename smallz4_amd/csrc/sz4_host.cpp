@@ -181,9 +181,8 @@ PipeArgs Pipe::args(uint32_t maxChain, const uint8_t* in, uint8_t* out, uint64_t
   a.dpRec = dpRec.as<uint4>();
   a.segState = segState.as<uint4>();
   a.lazySlots = work_at<uint32_t>(off.lazy);
-  a.walkSlots = work_at<uint32_t>(off.walk);
+  a.walkSlots = work_at<uint64_t>(off.tok);
   a.walkState = walkState.as<uint4>();
-  a.tokens = work_at<Token>(off.tok);
   a.ntok = ntok.as<uint32_t>();
   a.blockBytes = blockBytes.as<uint32_t>();
   a.offsets = offsets.as<uint64_t>();

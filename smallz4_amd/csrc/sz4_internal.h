@@ -34,7 +34,7 @@ struct Block {
   uint64_t start, end;     // [start, end)
   uint64_t low;            // lowest position a match may reference (reference dataZero)
   uint64_t cut;            // start-12 when the block re-inserts the previous tail (lookback), else kNone
-  uint64_t tokOff;         // first Token slot of this block (capacity (end-start)/2 + 4)
+  uint64_t tokOff;         // first 16-byte entry of this block in the Token area ((end-start)/2 + 4 of them)
   uint32_t prev;           // index of the previous block of the same stream, or kNoBlock
   uint32_t flags;          // kBlk* below
   uint32_t dpFirst;        // first DpSeg of this block (top segment first)
@@ -81,16 +81,19 @@ inline uint32_t dp_segment_size(uint64_t n) { return n <= 65536 ? 4096u : 8192u;
 constexpr uint32_t kMaxDpSegs = 2048;  // 8 MiB legacy block / 4096 (SZ4_DP_SIZE)
 
 // the token walk runs as sub-segments of kWalkSeg positions, each walked speculatively from its
-// first position and repaired by k_walk_fix; a sub-segment's match positions live in 2 * kWalkCap
-// u32 slots (speculative ones from kWalkCap on, repaired ones prepended below them)
+// first position and repaired by k_walk_fix; a sub-segment's matches live in 2 * walk_cap(r) slots of one
+// 8-byte match record each (sz4_match_rec.h; speculative ones from walk_cap(r) on, repaired ones prepended
+// below them), r being the sub-segment's positions
 constexpr uint32_t kWalkSeg = 4096;
 constexpr uint32_t kWalkCap = kWalkSeg / 4 + 2;
-
-// one LZ4 sequence: literal run [litFrom, litFrom+lits) (block-relative) then a match
-struct Token {
-  uint32_t litFrom, lits, mlen, dist;  // dist: low 16 bits; kTokLast marks the final literals-only token
-};
-constexpr uint32_t kTokLast = 0x80000000u;
+// matches of at least kMinMatch positions that start inside r positions, and two to spare: kWalkCap for a
+// full sub-segment, less for a block's last one
+constexpr uint32_t walk_cap(uint32_t r) { return r / 4 + 2 < kWalkCap ? r / 4 + 2 : kWalkCap; }
+// The slots lie in the plan's Token area (Plan::WorkOffsets::tok: 16 bytes for each of a block's
+// token_capacity(n) = n / 2 + 4 entries from Block::tokOff on, which is two records each): sub-segment k of a
+// block has the records from 2 * tokOff + k * kWalkSeg on.  A full sub-segment uses 2 * kWalkCap of its
+// kWalkSeg; the last one, of r positions, 2 * walk_cap(r) <= r / 2 + 4 of the r + 7 or more that remain.
+constexpr uint64_t walk_slot_first(uint64_t tokOff, uint32_t k) { return 2 * tokOff + (uint64_t)k * kWalkSeg; }
 
 // Sizes the planner (sz4_plan.cpp) shares with the kernels of sz4_kernels.hip that they are built for.
 // The finders' LDS-window kernels hold a 64 KiB block and 16 bytes more:
@@ -147,10 +150,9 @@ struct PipeArgs {
   uint4* dpRec;             // ... and one record per DpSeg
   uint4* segState;          // per DpSeg: the speculative parse's boundary state
   uint32_t* lazySlots;      // greedy/lazy replay: lazy_slots_per_walk() words per walk sub-segment
-  uint32_t* walkSlots;      // token walk: 2 * kWalkCap match positions per walk sub-segment
+  uint64_t* walkSlots;      // token walk: the match records (walk_slot_first), in the plan's Token area
   uint4* walkState;         // per walk sub-segment: the state of the replay, then of the token walk
-  Token* tokens;            // the frame's tokens (Block::tokOff)
-  uint32_t* ntok;           // per block: its token count
+  uint32_t* ntok;          // per block: its token count
   uint32_t* blockBytes;     // per block: its size word; until the token walk, the lazy check's first difference
   uint64_t* offsets;        // per block: its offset in the frame body (slot nblocks: the body's size)
   int* status;              // the device status word (kSt*)

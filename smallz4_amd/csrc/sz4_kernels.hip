@@ -13,7 +13,7 @@
 //   k_dp_spec / k_dp_fix    backward optimal parse as speculative segments + repair
 //                                                                      (smallz4.h:376-472)
 //   k_walk / k_walk_fix     forward walk of the parse choices          (smallz4.h:259-300)
-//   k_seg_scan, k_seg_tokens, k_block_bytes, k_scan, k_write_seg
+//   k_seg_scan, k_seg_sizes, k_block_bytes, k_scan, k_write_seg
 //                  tokens, sizes, stored/compressed decision, frame    (smallz4.h:300-371, 762-813)
 //   k_dict_matches dictionary mode: the reference's match loop replayed by one wavefront
 //
@@ -27,6 +27,7 @@
 
 #include "sz4_internal.h"
 #include "sz4_device.h"
+#include "sz4_match_rec.h"
 
 #ifndef SZ4_SKIP_SHIFT  // timing experiments only (results wrong): leave out a phase of k_find_sorted
 #define SZ4_SKIP_SHIFT 0
@@ -5600,18 +5601,21 @@ const Block* __restrict__ blocks, const DpSeg* __restrict__ dpSegs,
 // Sequences.  The reference walks the parse forward (selectBestMatches, smallz4.h:259-371): a
 // position with a chosen length > 1 starts a match, others are literals.  The walk is split into
 // sub-segments of kWalkSeg positions walked at once (k_walk), repaired where a speculative start
-// was wrong (k_walk_fix), and turned into 16-byte tokens (literal run, match) by k_seg_tokens.
+// was wrong (k_walk_fix); every match of the path is one 8-byte record (sz4_match_rec.h), from
+// which k_seg_sizes and k_write_seg derive the sequences (literal run, match).
 // ================================================================================================
 
 
 // k_walk: one wavefront per sub-segment walks the parse forward from the sub-segment's first
-// position as if a sequence started there, and records the positions of the matches it takes
-// until the walk reaches the next sub-segment.  Four 64-position windows of chosen lengths sit in
-// registers (loads run three windows ahead); literal stretches are skipped with one ballot.
+// position as if a sequence started there, and records the matches it takes (position, length and
+// distance: one record each, sz4_match_rec.h) until the walk reaches the next sub-segment.  The
+// 64-position windows of chosen lengths and of distances are loaded one window ahead; literal
+// stretches are skipped with one ballot.
 __global__ __launch_bounds__(64 * kWalkWaves) void k_walk(const Block* __restrict__ blocks,
                                                           const uint2* __restrict__ walkSegs, uint32_t nwalk,
                                                           const uint32_t* __restrict__ chosen,
-                                                          uint32_t* __restrict__ slotsAll, uint4* __restrict__ state,
+                                                          const uint16_t* __restrict__ mdist,
+                                                          uint64_t* __restrict__ slotsAll, uint4* __restrict__ state,
                                                           int* __restrict__ status)
 {
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -5623,9 +5627,11 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_walk(const Block* __restric
   if (ws.y >= B.walkCount) return;  // an inert entry of a sized queue's slot (sz4_slot_plan.h); uniform per wave
   const uint32_t n = (uint32_t)(B.end - B.start);
   const uint32_t* L = chosen + B.start;
-  uint32_t* slots = slotsAll + (uint64_t)idx * (2 * kWalkCap) + kWalkCap;
+  const uint16_t* D = mdist + B.start;
   const uint32_t a = ws.y * kWalkSeg;
   const uint32_t aNext = a + kWalkSeg < n ? a + kWalkSeg : n;
+  const uint32_t cap = walk_cap(aNext - a);
+  uint64_t* slots = slotsAll + walk_slot_first(B.tokOff, ws.y) + cap;
 
   // A window of 64 positions at a time, on the vector unit: lane l steps to l + max(1, chosen[l])
   // (F1, 64 = out of the window), F2 .. F32 by doubling (ds_bpermute), and every lane finds the last
@@ -5636,8 +5642,15 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_walk(const Block* __restric
     const uint32_t i = b + lane;
     return L[i < n ? i : n - 1u];
   };
+  // the distances of the same window, loaded as wL / nL are: unconditional with a clamped index, and used
+  // only where a lane records a match
+  auto ldd = [&](uint32_t b) -> uint32_t {
+    const uint32_t i = b + lane;
+    return D[i < n ? i : n - 1u];
+  };
   uint32_t wbase = a, e = 0, m = 0, exitPos = aNext;
   uint32_t wL = ldw(a), nL = ldw(a + 64);
+  uint32_t wD = ldd(a), nD = ldd(a + 64);
   while (true) {
     const uint32_t lim = aNext - wbase < 64u ? aNext - wbase : 64u;  // window positions before aNext
     const uint32_t len = wbase + lane < n && wL > 1u ? wL : 1u;
@@ -5650,11 +5663,13 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_walk(const Block* __restric
       const bool rec = x == lane && len > 1u && lane < lim;
       const uint64_t rb = __ballot(rec);
       const uint32_t cnt = (uint32_t)__builtin_popcountll(rb);
-      if (m + cnt > kWalkCap) {
+      if (m + cnt > cap) {
         if (lane == 0) atomicOr(status, kStInvariant);
         break;
       }
-      if (rec) slots[m + __builtin_amdgcn_mbcnt_hi((uint32_t)(rb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rb, 0u))] = wbase + lane;
+      if (rec)
+        slots[m + __builtin_amdgcn_mbcnt_hi((uint32_t)(rb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rb, 0u))] =
+            mrec_pack(wbase + lane, len, wD);
       m += cnt;
       const uint32_t p = rdlane(x, lim - 1u);  // the last path position before lim
       lastLen = rdlane(len, p);
@@ -5666,11 +5681,13 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_walk(const Block* __restric
     }
     const uint32_t nb = next & ~63u;
     wL = nb == wbase + 64u ? nL : ldw(nb);
+    wD = nb == wbase + 64u ? nD : ldd(nb);
     nL = ldw(nb + 64u);
+    nD = ldd(nb + 64u);
     wbase = nb;
     e = next & 63u;
   }
-  if (lane == 0) state[idx] = make_uint4(kWalkCap, kWalkCap + m, exitPos, 0u);
+  if (lane == 0) state[idx] = make_uint4(cap, cap + m, exitPos, 0u);
 }
 
 // Sub-segment repair.  Sub-segment k's walk is exact when the true path enters it at a position the
@@ -5686,42 +5703,44 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_walk(const Block* __restric
 //                     assumption held into place, and repairs the others again serially
 //                     (walk_repair) from their true entry.
 // walk_repair: the repair of sub-segment idx from `entry` (wave-uniform).  Returns the record; the
-// repaired matches are in fix[0, rec.y) (LDS).
+// repaired matches are in fix[0, rec.y): LDS in k_walk_fix_commit, whose destination depends on their
+// count; k_walk_fix_spec writes them straight to the lower half of the slots, which run() never reads.
 struct WalkRepair {
   const uint32_t* L;
-  const uint32_t* slots;  // the sub-segment's 2 * kWalkCap slots
+  const uint16_t* D;
+  const uint64_t* slots;  // the sub-segment's 2 * cap records
   uint32_t lane;
-  __device__ __forceinline__ uint4 run(uint32_t* fix, uint32_t a, uint32_t aNext, uint4 st, uint32_t entry, int* status) const
+  uint32_t cap;  // walk_cap of the sub-segment
+  __device__ __forceinline__ uint4 run(uint64_t* fix, uint32_t a, uint32_t aNext, uint4 st, uint32_t entry, int* status) const
   {
-    const uint32_t m = st.y - kWalkCap;
+    const uint32_t m = st.y - cap;
     if (entry == a) return make_uint4(st.x, 0u, st.z, entry);
     if (entry >= aNext) return make_uint4(st.y, 0u, entry, entry);
     // i = first speculative match at or after p (wave-parallel over 64 slots at a time)
     auto first_at = [&](uint32_t from, uint32_t p) -> uint32_t {
       for (uint32_t b = from; b < m; b += 64) {
-        const uint64_t ge = __ballot(b + lane < m && slots[kWalkCap + b + lane] >= p);
+        const uint64_t ge = __ballot(b + lane < m && mrec_pos(slots[cap + b + lane]) >= p);
         if (ge) return b + (uint32_t)__builtin_ctzll(ge);
       }
       return m;
     };
-    // q lies strictly inside speculative match i - 1
+    // q lies strictly inside speculative match i - 1 (its record holds its length)
     auto inside = [&](uint32_t i, uint32_t q) -> bool {
       if (i == 0) return false;
-      const uint32_t pj = slots[kWalkCap + i - 1];
-      return pj + L[pj] > q;
+      return mrec_end(slots[cap + i - 1]) > q;
     };
     uint32_t i = first_at(0, entry);
-    if (!inside(i, entry)) return make_uint4(kWalkCap + i, 0u, st.z, entry);
+    if (!inside(i, entry)) return make_uint4(cap + i, 0u, st.z, entry);
     uint32_t q = entry, f = 0;
     bool merged = false;
     while (q < aNext) {
       const uint32_t lq = L[q];
       if (lq > 1u) {
-        if (f >= kWalkCap) {
+        if (f >= cap) {
           if (lane == 0) atomicOr(status, kStInvariant);
           break;
         }
-        if (lane == 0) fix[f] = q;
+        if (lane == 0) fix[f] = mrec_pack(q, lq, D[q]);
         f++;
         q += lq;
       } else {
@@ -5734,18 +5753,18 @@ struct WalkRepair {
       }
     }
     const uint32_t iMerge = merged ? i : m;
-    return make_uint4(kWalkCap + iMerge - f, f, merged ? st.z : q, entry);
+    return make_uint4(cap + iMerge - f, f, merged ? st.z : q, entry);
   }
 };
 
 __global__ __launch_bounds__(64 * kWalkWaves) void k_walk_fix_spec(const Block* __restrict__ blocks,
                                                                    const uint2* __restrict__ walkSegs, uint32_t nwalk,
                                                                    const uint32_t* __restrict__ chosen,
-                                                                   uint32_t* __restrict__ slotsAll,
+                                                                   const uint16_t* __restrict__ mdist,
+                                                                   uint64_t* __restrict__ slotsAll,
                                                                    const uint4* __restrict__ state, uint4* __restrict__ rec,
                                                                    int* __restrict__ status)
 {
-  __shared__ uint32_t fixAll[kWalkWaves][kWalkCap];
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const uint32_t idx = blockIdx.x * kWalkWaves + wave;
   if (idx >= nwalk) return;
@@ -5756,28 +5775,27 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_walk_fix_spec(const Block* 
   if (ws.y >= B.walkCount) return;  // an inert entry of a sized queue's slot (sz4_slot_plan.h); uniform per wave
   const uint32_t n = (uint32_t)(B.end - B.start);
   const uint32_t a = ws.y * kWalkSeg, aNext = a + kWalkSeg < n ? a + kWalkSeg : n;
-  uint32_t* slots = slotsAll + (uint64_t)idx * (2 * kWalkCap);
-  const WalkRepair W{chosen + B.start, slots, lane};
-  uint32_t* fix = fixAll[wave];
-  // k_walk's exit of k - 1 (this kernel writes no state)
-  const uint4 r = W.run(fix, a, aNext, state[idx], state[idx - 1].z, status);
-  __builtin_amdgcn_wave_barrier();  // lane 0's fix[] stores before the other lanes read them
-  // repaired matches to the lower half [0, f): it holds nothing k_walk wrote
-  for (uint32_t t = lane; t < r.y; t += 64) slots[t] = fix[t];
+  uint64_t* slots = slotsAll + walk_slot_first(B.tokOff, ws.y);
+  const WalkRepair W{chosen + B.start, mdist + B.start, slots, lane, walk_cap(aNext - a)};
+  // k_walk's exit of k - 1 (this kernel writes no state); the repaired matches go to the lower half [0, f)
+  // of the slots: it holds nothing k_walk wrote
+  const uint4 r = W.run(slots, a, aNext, state[idx], state[idx - 1].z, status);
   if (lane == 0) rec[idx] = r;
 }
 
 __global__ __launch_bounds__(64) void k_walk_fix_commit(const Block* __restrict__ blocks, const uint32_t* __restrict__ chosen,
-                                                        uint32_t* __restrict__ slotsAll,
+                                                        const uint16_t* __restrict__ mdist,
+                                                        uint64_t* __restrict__ slotsAll,
                                                         uint4* __restrict__ state, const uint4* __restrict__ rec,
                                                         int* __restrict__ status)
 {
-  __shared__ uint32_t fix[kWalkCap];
+  __shared__ uint64_t fix[kWalkCap];
   const Block B = blocks[blockIdx.x];
   if (B.walkCount < 2) return;  // (also a sized queue's slot that is empty at this enqueue: no sub-segment)
   const uint32_t lane = threadIdx.x;
   const uint32_t n = (uint32_t)(B.end - B.start);
   const uint32_t* L = chosen + B.start;
+  const uint16_t* D = mdist + B.start;
   uint32_t T = state[B.walkFirst].z;  // true exit of sub-segment 0 (walked from the block start)
   for (uint32_t k0 = 1; k0 < B.walkCount; k0 += 64) {
     const uint32_t cnt = B.walkCount - k0 < 64u ? B.walkCount - k0 : 64u;
@@ -5792,7 +5810,7 @@ __global__ __launch_bounds__(64) void k_walk_fix_commit(const Block* __restrict_
       const uint32_t js = bad ? (uint32_t)__builtin_ctzll(bad) : cnt;
       if (lane >= cur && lane < js) {
         // the assumption held: move the repaired matches in place (destination above the source)
-        uint32_t* slots = slotsAll + (uint64_t)idxL * (2 * kWalkCap);
+        uint64_t* slots = slotsAll + walk_slot_first(B.tokOff, k0 + lane);
         for (uint32_t t = r.y; t-- > 0;) slots[r.x + t] = slots[t];
         uint32_t* s32 = reinterpret_cast<uint32_t*>(state + idxL);
         s32[0] = r.x;
@@ -5805,8 +5823,8 @@ __global__ __launch_bounds__(64) void k_walk_fix_commit(const Block* __restrict_
       // sub-segment k0 + js entered elsewhere: repaired again from its true entry
       const uint32_t idx = B.walkFirst + k0 + js;
       const uint32_t a = (k0 + js) * kWalkSeg, aNext = a + kWalkSeg < n ? a + kWalkSeg : n;
-      uint32_t* slots = slotsAll + (uint64_t)idx * (2 * kWalkCap);
-      const WalkRepair W{L, slots, lane};
+      uint64_t* slots = slotsAll + walk_slot_first(B.tokOff, k0 + js);
+      const WalkRepair W{L, D, slots, lane, walk_cap(aNext - a)};
       const uint4 st = state[idx];
       const uint4 rr = W.run(fix, a, aNext, st, rdlane(prevExit, js), status);
       __syncthreads();
@@ -5817,16 +5835,6 @@ __global__ __launch_bounds__(64) void k_walk_fix_commit(const Block* __restrict_
       cur = js + 1;
     }
   }
-}
-
-__device__ __forceinline__ uint64_t token_bytes(uint64_t lits, uint32_t mlen, bool last)
-{
-  uint64_t b = 1 + lits + (lits >= 15 ? (lits - 15) / 255 + 1 : 0);
-  if (!last) {
-    const int64_t mcode = (int64_t)mlen - kMinMatch;
-    b += 2 + (mcode >= 15 ? (uint64_t)(mcode - 15) / 255 + 1 : 0);
-  }
-  return b;
 }
 
 // ================================================================================================
@@ -5862,15 +5870,17 @@ constexpr uint64_t kOwnLits = 64;  // longer literal runs are copied by the whol
 // Frame assembly by walk sub-segment (kWalkSeg positions), so that large blocks fill the GPU too:
 //   k_seg_scan    per block: exclusive scans over its sub-segments of the match counts (token base)
 //                 and of the match ends (the end of the last match before the sub-segment)
-//   k_seg_tokens  per sub-segment: its tokens (literal run + match, smallz4.h:259-371), their byte
-//                 sizes summed; the block's last sub-segment adds the closing literal run
+//   k_seg_sizes   per sub-segment: the byte sizes of its sequences (literal run + match,
+//                 smallz4.h:259-371) summed, each literal run taken from the end of the match record
+//                 before; the block's last sub-segment sizes the closing literal run
 //   k_block_bytes per block: byte offsets of the sub-segments, encoded size, stored/compressed
 //                 decision (smallz4.h:764-771)
 //   k_scan        block offsets in the frame
-//   k_write_seg   per sub-segment: its tokens (or its raw bytes) at their place in the frame
+//   k_write_seg   per sub-segment: its sequences (or its raw bytes) at their place in the frame, from
+//                 the same match records
 // ================================================================================================
 constexpr int kAsmThreads = 1024;
-constexpr int kSegWaves = 4;  // sub-segments per k_seg_tokens / k_write_seg workgroup
+constexpr int kSegWaves = 4;  // sub-segments per k_seg_sizes / k_write_seg workgroup
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 {
@@ -5880,14 +5890,13 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 }
 
 // info[idx] = (token base, end of the last match before, byte size, byte offset) per sub-segment
-__global__ __launch_bounds__(kAsmThreads) void k_seg_scan(const Block* __restrict__ blocks, const uint32_t* __restrict__ chosen,
-                                                          const uint32_t* __restrict__ slotsAll,
+__global__ __launch_bounds__(kAsmThreads) void k_seg_scan(const Block* __restrict__ blocks,
+                                                          const uint64_t* __restrict__ slotsAll,
                                                           const uint4* __restrict__ state, uint4* __restrict__ info)
 {
   __shared__ uint32_t s_sum[kAsmThreads / 64], s_max[kAsmThreads / 64];
   const Block B = blocks[blockIdx.x];
   if (B.start == B.end) return;  // a sized queue's slot that is empty at this enqueue; uniform
-  const uint32_t* L = chosen + B.start;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   uint32_t carrySum = 0, carryMax = 0;
   for (uint32_t k0 = 0; k0 < B.walkCount; k0 += kAsmThreads) {
@@ -5898,10 +5907,7 @@ __global__ __launch_bounds__(kAsmThreads) void k_seg_scan(const Block* __restric
     if (valid) {
       const uint4 st = state[idx];
       cnt = st.y - st.x;
-      if (cnt) {
-        const uint32_t p = slotsAll[(uint64_t)idx * (2 * kWalkCap) + st.y - 1];
-        lastEnd = p + L[p];
-      }
+      if (cnt) lastEnd = mrec_end(slotsAll[walk_slot_first(B.tokOff, k) + st.y - 1]);
     }
     const uint32_t incS = wave_incl_scan_add(cnt), incM = wave_incl_scan_max(lastEnd);
     uint32_t prevM = __shfl_up(incM, 1, 64);
@@ -5925,13 +5931,11 @@ __global__ __launch_bounds__(kAsmThreads) void k_seg_scan(const Block* __restric
   }
 }
 
-// tokens of one sub-segment; blockTail[b] = (matches of the block, bytes of its closing literal run)
-__global__ __launch_bounds__(64 * kSegWaves) void k_seg_tokens(const Block* __restrict__ blocks, const uint2* __restrict__ walkSegs,
-                                                              uint32_t nwalk, const uint32_t* __restrict__ chosen,
-                                                              const uint16_t* __restrict__ mdist,
-                                                              const uint32_t* __restrict__ slotsAll, const uint4* __restrict__ state,
-                                                              uint4* __restrict__ info, Token* __restrict__ tokAll,
-                                                              uint2* __restrict__ blockTail)
+// sizes of one sub-segment's sequences; blockTail[b] = (matches of the block, bytes of its closing literal run)
+__global__ __launch_bounds__(64 * kSegWaves) void k_seg_sizes(const Block* __restrict__ blocks, const uint2* __restrict__ walkSegs,
+                                                             uint32_t nwalk, const uint64_t* __restrict__ slotsAll,
+                                                             const uint4* __restrict__ state, uint4* __restrict__ info,
+                                                             uint2* __restrict__ blockTail)
 {
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const uint32_t idx = blockIdx.x * kSegWaves + wave;
@@ -5941,47 +5945,28 @@ __global__ __launch_bounds__(64 * kSegWaves) void k_seg_tokens(const Block* __re
   const Block B = blocks[ws.x];
   if (ws.y >= B.walkCount) return;  // an inert entry of a sized queue's slot (sz4_slot_plan.h); uniform per wave
   const uint32_t n = (uint32_t)(B.end - B.start);
-  const uint32_t* L = chosen + B.start;
-  const uint16_t* D = mdist + B.start;
   const uint4 st = state[idx];
   const uint4 inf = info[idx];
   const uint32_t m = st.y - st.x;
-  const uint32_t* slots = slotsAll + (uint64_t)idx * (2 * kWalkCap);
-  Token* tok = tokAll + B.tokOff + inf.x;
+  const uint64_t* recs = slotsAll + walk_slot_first(B.tokOff, ws.y) + st.x;
   uint32_t carryEnd = inf.y, bytes = 0;
-  // loads run ahead: the next batch's match positions, then their lengths and distances
-  uint32_t pN = lane < m ? slots[st.x + lane] : 0u;
-  uint32_t LN = lane < m ? L[pN] : 0u, DN = lane < m ? (uint32_t)D[pN] : 0u;
-  uint32_t pNN = 64u + lane < m ? slots[st.x + 64u + lane] : 0u;
+  // the next batch's records are loaded one batch ahead
+  uint64_t rN = lane < m ? recs[lane] : 0ull;
   for (uint32_t c0 = 0; c0 < m; c0 += 64) {
     const uint32_t t = c0 + lane;
-    const bool valid = t < m;
-    uint32_t p, Lm, Dm;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(p) : "v"(pN));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(Lm) : "v"(LN));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(Dm) : "v"(DN));
-    pN = pNN;
-    LN = t + 64u < m ? L[pN] : 0u;
-    DN = t + 64u < m ? (uint32_t)D[pN] : 0u;
-    pNN = t + 128u < m ? slots[st.x + t + 128u] : 0u;
-    const uint32_t end = p + Lm;
+    const uint64_t r = rN;
+    rN = t + 64u < m ? recs[t + 64u] : 0ull;
+    const uint32_t p = mrec_pos(r), Lm = mrec_len(r), end = p + Lm;
     uint32_t prev = __shfl_up(end, 1, 64);
     if (lane == 0) prev = carryEnd;
-    uint32_t sz = 0;
-    if (valid) {
-      const uint32_t lits = p - prev;
-      tok[t] = Token{lits ? prev : 0u, lits, Lm, Dm};
-      sz = (uint32_t)token_bytes(lits, Lm, false);
-    }
-    bytes += wave_sum_u32(sz);
+    if (t < m) bytes += (uint32_t)token_bytes(p - prev, Lm, false);
     carryEnd = rdlane(end, m - c0 < 64 ? m - c0 - 1 : 63);
   }
+  bytes = wave_sum_u32(bytes);
   if (lane == 0) info[idx].z = bytes;
   if (ws.y + 1 == B.walkCount && lane == 0) {
-    // the closing literal run (kTokLast)
-    const uint32_t M = inf.x + m;
-    tokAll[B.tokOff + M] = Token{carryEnd, n - carryEnd, 0u, kTokLast};
-    blockTail[ws.x] = make_uint2(M, (uint32_t)token_bytes(n - carryEnd, 0, true));
+    // the closing literal run, from the end of the block's last match
+    blockTail[ws.x] = make_uint2(inf.x + m, (uint32_t)token_bytes(n - carryEnd, 0, true));
   }
 }
 
@@ -6027,7 +6012,7 @@ __global__ __launch_bounds__(kAsmThreads) void k_block_bytes(const Block* __rest
   }
   const bool useEnc = (enc < n && !stored) || legacy;
   const uint32_t bytes = (uint32_t)(useEnc ? enc : n);
-  // a block's tokens fit its Token slots ((n / 2 + 4), one match per >= 4 bytes) and its size word
+  // a block's tokens number at most n / 2 + 4 (token_capacity: one match per >= 4 bytes) and its bytes fit its size word
   if (tid == 0 && (ntok > n / 2 + 4 || (useEnc ? enc : n) >= 0x7FFFFFFBull)) atomicOr(status, kStInvariant);
   if (tid == 0) {
     ntokOut[blockIdx.x] = useEnc ? ntok : 0u;
@@ -6039,7 +6024,7 @@ __global__ __launch_bounds__(kAsmThreads) void k_block_bytes(const Block* __rest
 __global__ __launch_bounds__(64 * kSegWaves) void k_write_seg(const uint8_t* __restrict__ in, const Block* __restrict__ blocks,
                                                              const uint2* __restrict__ walkSegs, uint32_t nwalk,
                                                              const uint4* __restrict__ state, const uint4* __restrict__ info,
-                                                             const Token* __restrict__ tokAll, const uint32_t* __restrict__ ntokAll,
+                                                             const uint64_t* __restrict__ slotsAll, const uint32_t* __restrict__ ntokAll,
                                                              const uint32_t* __restrict__ blockBytes,
                                                              const uint64_t* __restrict__ offsets, uint8_t* __restrict__ out,
                                                              uint64_t headerLen)
@@ -6072,20 +6057,27 @@ __global__ __launch_bounds__(64 * kSegWaves) void k_write_seg(const uint8_t* __r
   }
   if (ntokAll[ws.x] == 0) return;  // legacy frame at level 0: an empty compressed block
   const uint4 st = state[idx], inf = info[idx];
-  const uint32_t count = (st.y - st.x) + (ws.y + 1 == B.walkCount ? 1u : 0u);
-  const Token* tok = tokAll + B.tokOff + inf.x;
+  // the sub-segment's sequences: one per match record, its literal run reaching back to the end of the match
+  // before (inf.y for the first); the block's last sub-segment appends the closing literal run, from the end
+  // of the block's last match to the block's end
+  const uint32_t m = st.y - st.x;
+  const uint32_t count = m + (ws.y + 1 == B.walkCount ? 1u : 0u);
+  const uint64_t* recs = slotsAll + walk_slot_first(B.tokOff, ws.y) + st.x;
   uint64_t carry = inf.w;
+  uint32_t carryEnd = inf.y;
   for (uint32_t c0 = 0; c0 < count; c0 += 64) {
     const uint32_t t = c0 + lane;
     const bool valid = t < count;
-    Token T{0, 0, 0, 0};
-    uint64_t sz = 0;
-    bool last = false;
-    if (valid) {
-      T = tok[t];
-      last = (T.dist & kTokLast) != 0;
-      sz = token_bytes(T.lits, T.mlen, last);
-    }
+    const bool last = valid && t == m;
+    const uint64_t r = t < m ? recs[t] : 0ull;
+    const uint32_t end = mrec_end(r);
+    uint32_t litFrom = __shfl_up(end, 1, 64);
+    if (lane == 0) litFrom = carryEnd;
+    if (m > c0) carryEnd = rdlane(end, m - c0 < 64 ? m - c0 - 1 : 63);  // wave-uniform
+    const struct {
+      uint32_t litFrom, lits, mlen, dist;
+    } T{litFrom, (last ? (uint32_t)n : mrec_pos(r)) - litFrom, mrec_len(r), mrec_dist(r)};
+    const uint64_t sz = valid ? token_bytes(T.lits, T.mlen, last) : 0;
     uint64_t incl = sz;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -6276,22 +6268,22 @@ void launch_emit(const PipeArgs& a, hipStream_t s)
   uint4* info = reinterpret_cast<uint4*>(a.reach);
   uint2* blockTail = reinterpret_cast<uint2*>(info + a.nwalk);
   if (walk) {
-    hipLaunchKernelGGL(k_walk, walks, walkBlock, 0, s, a.blocks, a.walkSegs, a.nwalk, a.chosen, a.walkSlots, a.walkState,
-                       a.status);
-    hipLaunchKernelGGL(k_walk_fix_spec, walks, walkBlock, 0, s, a.blocks, a.walkSegs, a.nwalk, a.chosen, a.walkSlots,
+    // (the distances are the finders' whether the walk follows sel or mlen)
+    hipLaunchKernelGGL(k_walk, walks, walkBlock, 0, s, a.blocks, a.walkSegs, a.nwalk, a.chosen, a.mdist, a.walkSlots,
+                       a.walkState, a.status);
+    hipLaunchKernelGGL(k_walk_fix_spec, walks, walkBlock, 0, s, a.blocks, a.walkSegs, a.nwalk, a.chosen, a.mdist, a.walkSlots,
                        a.walkState, info, a.status);
-    hipLaunchKernelGGL(k_walk_fix_commit, dim3(a.nblocks), dim3(64), 0, s, a.blocks, a.chosen, a.walkSlots, a.walkState,
-                       info, a.status);
-    hipLaunchKernelGGL(k_seg_scan, dim3(a.nblocks), dim3(kAsmThreads), 0, s, a.blocks, a.chosen, a.walkSlots, a.walkState,
-                       info);
-    hipLaunchKernelGGL(k_seg_tokens, segGrid, segBlock, 0, s, a.blocks, a.walkSegs, a.nwalk, a.chosen, a.mdist, a.walkSlots,
-                       a.walkState, info, a.tokens, blockTail);
+    hipLaunchKernelGGL(k_walk_fix_commit, dim3(a.nblocks), dim3(64), 0, s, a.blocks, a.chosen, a.mdist, a.walkSlots,
+                       a.walkState, info, a.status);
+    hipLaunchKernelGGL(k_seg_scan, dim3(a.nblocks), dim3(kAsmThreads), 0, s, a.blocks, a.walkSlots, a.walkState, info);
+    hipLaunchKernelGGL(k_seg_sizes, segGrid, segBlock, 0, s, a.blocks, a.walkSegs, a.nwalk, a.walkSlots, a.walkState, info,
+                       blockTail);
   }
   hipLaunchKernelGGL(k_block_bytes, dim3(a.nblocks), dim3(kAsmThreads), 0, s, a.blocks, a.maxChain, info, blockTail, a.ntok,
                      a.blockBytes, a.status);
   hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, a.blockBytes, a.nblocks, a.offsets);
   if (a.nwalk)
-    hipLaunchKernelGGL(k_write_seg, segGrid, segBlock, 0, s, a.in, a.blocks, a.walkSegs, a.nwalk, a.walkState, info, a.tokens,
+    hipLaunchKernelGGL(k_write_seg, segGrid, segBlock, 0, s, a.in, a.blocks, a.walkSegs, a.nwalk, a.walkState, info, a.walkSlots,
                        a.ntok, a.blockBytes, a.offsets, a.out, a.headerLen);
 }
 

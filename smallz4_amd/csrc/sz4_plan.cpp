@@ -121,7 +121,9 @@ uint64_t Plan::work_layout(uint64_t stagedBytes)
   off.lazy = selBytes;
   const uint64_t lazyEnd = off.lazy + al(walk.size() * lazy_slots_per_walk() * 4ull + 64);
   off.tok = selBytes;
-  off.walk = off.tok + al(tokTotal * sizeof(Token) + 64);
+  // the Token area, 16 bytes per entry, holds the token walk's 8-byte match records (walk_slot_first); the
+  // walk area behind it keeps its place and size and is unused
+  off.walk = off.tok + al(tokTotal * 16 + 64);
   const uint64_t emitEnd = off.walk + al(walk.size() * 2 * kWalkCap * 4 + 64);
   return std::max(std::max(findEnd, parseEnd), std::max(lazyEnd, emitEnd));
 }

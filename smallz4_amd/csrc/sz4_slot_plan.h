@@ -27,7 +27,7 @@ namespace sz4 {
 
 struct Slot {
   uint64_t start;      // first staged byte (a multiple of kBatchAlign)
-  uint64_t tokOff;     // first Token slot (token_capacity(cap) of them)
+  uint64_t tokOff;     // first Token slot (token_capacity(cap) of them: the token walk's match records)
   uint64_t elemOff;    // first sort element
   uint64_t rankOff;    // first rank entry
   uint32_t cap;        // the largest size an enqueue may give the item
