@@ -160,6 +160,41 @@ int sz4_unlz4_batch_typed_device(sz4_ctx* ctx, const void* d_blocks, const uint6
  * sz4_set_timing on; 0 when every width was 1). */
 float sz4_last_merge_ms(sz4_ctx* ctx);
 
+/* ---- filtered items: the bit-plane shuffle (the "bitshuffle" of HDF5 and Blosc) beside the byte-plane split ----
+ * LZ4 has no entropy stage: a byte plane of a few frequent values gains nothing, a constant BIT plane is a run.
+ * An item of n bytes and element width E (1, 2, 4 or 8) has m = n / E whole elements, of which g = m - m % 8 are
+ * shuffled into 8 * E bit rows of G = g / 8 bytes each (bits numbered from the least significant):
+ *     bit (e & 7) of shuf[(8 * k + b) * G + (e >> 3)] = bit b of item[e * E + k]   (0 <= k < E, 0 <= b < 8, 0 <= e < g)
+ *     shuf[j] = item[j]                                                            (g * E <= j < n)
+ * -- the byte-plane split of the first g elements with every plane bit-transposed into its 8 rows; the m % 8
+ * left-over elements and the n % E tail bytes keep their place after the rows.  It changes no size, is the
+ * identity for g = 0 (n < 8 * E), and E = 1 is meaningful (the bit rows of the bytes).  smallz4_amd/planes.py
+ * states both directions in numpy (bit_split, bit_merge). */
+#define SZ4_FILTER_BYTES 0 /* the byte-plane split: what the typed calls do */
+#define SZ4_FILTER_BITS 1  /* the bit-plane shuffle above                   */
+
+/* As sz4_compress_batch_typed_device with a filter per item: filters is a HOST array of count bytes, each
+ * SZ4_FILTER_BYTES or SZ4_FILTER_BITS.  filters == NULL, or SZ4_FILTER_BYTES throughout, is exactly the typed call
+ * (same code path, same bytes).  Any other filter value, or a width other than 1, 2, 4 or 8: SZ4_E_ARG before
+ * any device work, nothing written.  Item i's block is exactly what smallz4::lz4 emits for the filtered item on
+ * its own -- for SZ4_FILTER_BITS shuf(item i, E_i) -- an ordinary LZ4 block that any decoder reads, giving the
+ * filtered bytes.  The shuffle happens while the item is staged, at no extra pass over the data; a batch whose
+ * widths are all 1 but which has a SZ4_FILTER_BITS item is not the plain call.  sz4_batch_bound, out_offsets,
+ * sz4_last_block_sizes, the pieces and sz4_last_gather_ms are as in the typed call. */
+int sz4_compress_batch_filtered_device(sz4_ctx* ctx, const void* const* in_ptrs, const uint32_t* in_sizes,
+                                       const uint8_t* elem_sizes, const uint8_t* filters, uint64_t count,
+                                       uint32_t max_chain, void* d_out, uint64_t out_cap, uint64_t* out_offsets,
+                                       void* stream);
+
+/* As sz4_unlz4_batch_typed_device with a filter per item (filters as above; NULL or SZ4_FILTER_BYTES throughout is
+ * exactly the typed call): item i's decoded bytes pass through the inverse of its filter on their way to d_out.
+ * d_out may have any alignment; a SZ4_FILTER_BITS item is unshuffled 8 elements at a time with 16-byte stores
+ * where it lands at a multiple of 8 (E = 1), 16 (E = 2), 32 (E = 4) or 64 (E = 8) bytes, counted from the 16-byte
+ * boundary at or below d_out, and bit by bit elsewhere.  Same query mode, same error codes, sz4_last_merge_ms as in the typed call. */
+int sz4_unlz4_batch_filtered_device(sz4_ctx* ctx, const void* d_blocks, const uint64_t* offsets,
+                                    const uint8_t* elem_sizes, const uint8_t* filters, uint64_t count, void* d_out,
+                                    uint64_t out_cap, uint64_t* out_offsets, void* stream);
+
 /* ---- decode queue: the batch decoders as an enqueue, nothing on the host ---------------------------------
  * sz4_unlz4_batch_device takes host tables, waits for the stream twice and fails as a whole on one bad item.
  * A decode queue takes DEVICE tables, writes per-item sizes and statuses on the device and only launches:

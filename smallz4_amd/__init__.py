@@ -14,7 +14,8 @@ plus the data-parallel entry point the GPU is built for:
         -> many separate buffers of different sizes, one independently decodable LZ4 block each
     Compressor().compress_batch_typed(items, elem_sizes) / unlz4_batch_typed(blocks, elem_sizes)
     Compressor().compress_tensor(t) / decompress_tensor(ct)
-        -> the same for items of fixed-width elements, split into byte planes (planes.py) on the way
+        -> the same for items of fixed-width elements, split into byte planes (planes.py) on the way;
+           filters="bits" / filter="bits" shuffles them into bit planes instead (planes.bit_split)
     Compressor().decode_queue(max_items, max_src_bytes) -> DecodeQueue.enqueue(...) / tensor_tables(ct, out)
         -> the batch decoders as an enqueue over device tables: no host synchronisation, graph-capturable
     Compressor().compress_queue(sizes, elems, max_chain_length) -> CompressQueue.enqueue(...) / tensor_tables(t)
@@ -39,6 +40,9 @@ MaxChainLength = 65535  # smallz4.h:115 ("-9")
 # per-stage device timings reported by sz4_last_stage_ms (include/smallz4_amd.h)
 STAGES = ("runs", "sort", "find_sorted", "find_long", "parse", "assemble")
 
+# the per-item filters of the filtered batch calls (SZ4_FILTER_* in include/smallz4_amd.h)
+FILTERS = {"bytes": _native.SZ4_FILTER_BYTES, "bits": _native.SZ4_FILTER_BITS}
+
 HEADERS = {"smallz4": _native.SZ4_HEADER_SMALLZ4, "independent": _native.SZ4_HEADER_INDEPENDENT,
            "none": _native.SZ4_HEADER_NONE}
 
@@ -62,6 +66,7 @@ class CompressedTensor:
     dtype: object        # the tensor's torch dtype (its element size is every chunk's width)
     shape: tuple
     chunk_bytes: int     # bytes of the tensor per chunk (the last chunk holds the rest)
+    filter: str = "bytes"  # every chunk's filter: "bytes" (planes.split) or "bits" (planes.bit_split)
 
     @property
     def nbytes(self) -> int:
@@ -144,6 +149,8 @@ class DecodeQueue:
         the device), built once: chunk pointers cut from ct.blocks and from out, every width the dtype's.
         Enqueue them, or replay a captured enqueue, any number of times."""
         import torch
+        if getattr(ct, "filter", "bytes") != "bytes":
+            raise ValueError("the decode queue merges byte planes only: decode a filter='bits' tensor with decompress_tensor")
         dev = torch.device("cuda", self.device)
         if out.dtype != ct.dtype or tuple(out.shape) != tuple(ct.shape) or not out.is_contiguous() or out.device != dev:
             raise TypeError("out must be a contiguous device tensor of the compressed tensor's dtype and shape")
@@ -555,10 +562,64 @@ class Compressor:
             self._check(rc, "sz4_unlz4_batch_typed_device")
         return list(res)
 
-    def compress_batch_typed(self, items, elem_sizes=None, max_chain_length: int = MaxChainLength) -> list[bytes]:
+    # -- filtered ragged batch: the bit-plane shuffle (planes.bit_split) beside the byte-plane split --
+    def compress_batch_filtered_device(self, ptrs, sizes, elems, filters, d_out: int, out_cap: int,
+                                       max_chain_length: int = MaxChainLength, stream: int = 0) -> list[int]:
+        """compress_batch_typed_device with a filter per item (SZ4_FILTER_BYTES / SZ4_FILTER_BITS, or None for
+        the typed call): a BITS item's block is oz_block(planes.bit_split(item i, elems[i])) (see
+        sz4_compress_batch_filtered_device)."""
+        count = len(sizes)
+        if len(ptrs) != count or len(elems) != count or (filters is not None and len(filters) != count):
+            raise ValueError("ptrs, sizes, elems and filters differ in length")
+        p = (ctypes.c_void_p * max(count, 1))(*[int(x) or None for x in ptrs])
+        z = (ctypes.c_uint32 * max(count, 1))(*[int(x) for x in sizes])
+        w = (ctypes.c_uint8 * max(count, 1))(*[int(x) & 0xFF if 0 <= int(x) < 256 else 0 for x in elems])
+        f = None if filters is None else (ctypes.c_uint8 * max(count, 1))(*[int(x) if 0 <= int(x) < 256 else 255 for x in filters])
+        off = (ctypes.c_uint64 * (count + 1))()
+        rc = self._lib.sz4_compress_batch_filtered_device(self._h, p, z, w, f, count, int(max_chain_length),
+                                                          ctypes.c_void_p(d_out), out_cap, off, ctypes.c_void_p(stream))
+        self._check(rc, "sz4_compress_batch_filtered_device")
+        return list(off)
+
+    def unlz4_batch_filtered_device(self, d_blocks: int, offsets, elems, filters, d_out: int, out_cap: int,
+                                    stream: int = 0) -> list[int]:
+        """unlz4_batch_typed_device with a filter per item (as above): a BITS item passes through
+        planes.bit_merge on its way to d_out (see sz4_unlz4_batch_filtered_device)."""
+        count = len(offsets) - 1
+        if count < 0:
+            raise ValueError("offsets needs count + 1 entries")
+        if len(elems) != count or (filters is not None and len(filters) != count):
+            raise ValueError("offsets, elems and filters differ in length")
+        o = (ctypes.c_uint64 * (count + 1))(*[int(x) for x in offsets])
+        w = (ctypes.c_uint8 * max(count, 1))(*[int(x) & 0xFF if 0 <= int(x) < 256 else 0 for x in elems])
+        f = None if filters is None else (ctypes.c_uint8 * max(count, 1))(*[int(x) if 0 <= int(x) < 256 else 255 for x in filters])
+        res = (ctypes.c_uint64 * (count + 1))()
+        rc = self._lib.sz4_unlz4_batch_filtered_device(self._h, ctypes.c_void_p(d_blocks), o, w, f, count,
+                                                       ctypes.c_void_p(d_out), out_cap, res, ctypes.c_void_p(stream))
+        if not (rc == _native.SZ4_E_CAPACITY and not d_out and not out_cap):
+            self._check(rc, "sz4_unlz4_batch_filtered_device")
+        return list(res)
+
+    @staticmethod
+    def _filters(filters, count):
+        """"bytes" / "bits" per item, or one string for all -> SZ4_FILTER_* per item; None stays None."""
+        if filters is None:
+            return None
+        if isinstance(filters, str):
+            filters = [filters] * count
+        if len(filters) != count:
+            raise ValueError("items and filters differ in length")
+        for f in filters:
+            if f not in FILTERS:
+                raise ValueError(f"filter {f!r} is not 'bytes' or 'bits'")
+        return [FILTERS[f] for f in filters]
+
+    def compress_batch_typed(self, items, elem_sizes=None, max_chain_length: int = MaxChainLength, filters=None) -> list[bytes]:
         """compress_batch for typed items: [oz_block(planes.split(item, E)) for item in items].  A torch tensor
         of any dtype is taken as its bytes with E = its element size (1, 2, 4 or 8; any other: TypeError);
-        a bytes-like needs its width in elem_sizes (one entry per item; None for a tensor = its dtype's)."""
+        a bytes-like needs its width in elem_sizes (one entry per item; None for a tensor = its dtype's).
+        filters: "bytes" or "bits" per item, or one string for all; a "bits" item's block is
+        oz_block(planes.bit_split(item, E))."""
         import torch
         dev = torch.device("cuda", self.device)
         if elem_sizes is not None and len(elem_sizes) != len(items):
@@ -583,16 +644,22 @@ class Compressor:
         cap = self.batch_bound(sizes)
         out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        off = self.compress_batch_typed_device([v.data_ptr() if n else 0 for v, n in zip(views, sizes)], sizes, elems,
-                                               out.data_ptr(), cap, max_chain_length, stream)
+        ptrs = [v.data_ptr() if n else 0 for v, n in zip(views, sizes)]
+        if filters is None:
+            off = self.compress_batch_typed_device(ptrs, sizes, elems, out.data_ptr(), cap, max_chain_length, stream)
+        else:
+            off = self.compress_batch_filtered_device(ptrs, sizes, elems, self._filters(filters, len(sizes)), out.data_ptr(),
+                                                      cap, max_chain_length, stream)
         raw = out[:off[-1]].cpu().numpy().tobytes()
         return [raw[off[i]:off[i + 1]] for i in range(len(sizes))]
 
-    def unlz4_batch_typed(self, blocks, elem_sizes) -> list[bytes]:
-        """The reverse of compress_batch_typed: every bare block decoded on its own and merged by its width."""
+    def unlz4_batch_typed(self, blocks, elem_sizes, filters=None) -> list[bytes]:
+        """The reverse of compress_batch_typed: every bare block decoded on its own and merged by its width
+        (and its filter, given as there)."""
         import torch
         dev = torch.device("cuda", self.device)
         blocks = [bytes(b) for b in blocks]
+        filters = self._filters(filters, len(blocks))
         offsets = [0]
         for b in blocks:
             offsets.append(offsets[-1] + len(b))
@@ -600,14 +667,22 @@ class Compressor:
         d = (torch.frombuffer(joined, dtype=torch.uint8).to(dev) if joined
              else torch.empty(16, dtype=torch.uint8, device=dev))
         stream = torch.cuda.current_stream(dev).cuda_stream
-        sizes = self.unlz4_batch_typed_device(d.data_ptr(), offsets, elem_sizes, 0, 0, stream)
+
+        def decode(d_out, cap):
+            if filters is None:
+                return self.unlz4_batch_typed_device(d.data_ptr(), offsets, elem_sizes, d_out, cap, stream)
+            return self.unlz4_batch_filtered_device(d.data_ptr(), offsets, elem_sizes, filters, d_out, cap, stream)
+
+        sizes = decode(0, 0)
         out = torch.empty(max(sizes[-1], 16), dtype=torch.uint8, device=dev)
-        off = self.unlz4_batch_typed_device(d.data_ptr(), offsets, elem_sizes, out.data_ptr(), sizes[-1], stream)
+        off = decode(out.data_ptr(), sizes[-1])
         raw = out[:off[-1]].cpu().numpy().tobytes()
         return [raw[off[i]:off[i + 1]] for i in range(len(blocks))]
 
-    def compress_tensor(self, t, chunk_bytes: int = 65536, max_chain_length: int = MaxChainLength) -> "CompressedTensor":
-        """A tensor as typed blocks of chunk_bytes each (the last one shorter), all of width t.element_size().
+    def compress_tensor(self, t, chunk_bytes: int = 65536, max_chain_length: int = MaxChainLength,
+                        filter: str = "bytes") -> "CompressedTensor":
+        """A tensor as typed blocks of chunk_bytes each (the last one shorter), all of width t.element_size()
+        and of one filter ("bytes": the byte-plane split; "bits": the bit-plane shuffle).
         The tensor is made contiguous and cut by pointer: its payload is not copied, and the blocks stay on
         the device -- only their offsets come to the host."""
         import torch
@@ -617,6 +692,8 @@ class Compressor:
             raise TypeError(f"element width {e} is not 1, 2, 4 or 8")
         if not 0 < chunk_bytes <= 4 << 20 or chunk_bytes % e:
             raise ValueError("chunk_bytes must be a multiple of the element size, at most 4 MiB")
+        if filter not in FILTERS:
+            raise ValueError(f"filter {filter!r} is not 'bytes' or 'bits'")
         flat = t.detach().to(dev).contiguous().reshape(-1).view(torch.uint8)
         n = flat.numel()
         sizes = [min(chunk_bytes, n - o) for o in range(0, n, chunk_bytes)]
@@ -624,9 +701,13 @@ class Compressor:
         cap = self.batch_bound(sizes)
         out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        off = self.compress_batch_typed_device([base + k * chunk_bytes for k in range(len(sizes))], sizes,
-                                               [e] * len(sizes), out.data_ptr(), cap, max_chain_length, stream)
-        return CompressedTensor(out[:off[-1]].clone(), off, t.dtype, tuple(t.shape), chunk_bytes)
+        ptrs = [base + k * chunk_bytes for k in range(len(sizes))]
+        if filter == "bytes":
+            off = self.compress_batch_typed_device(ptrs, sizes, [e] * len(sizes), out.data_ptr(), cap, max_chain_length, stream)
+        else:
+            off = self.compress_batch_filtered_device(ptrs, sizes, [e] * len(sizes), [FILTERS[filter]] * len(sizes),
+                                                      out.data_ptr(), cap, max_chain_length, stream)
+        return CompressedTensor(out[:off[-1]].clone(), off, t.dtype, tuple(t.shape), chunk_bytes, filter)
 
     def decompress_tensor(self, ct: "CompressedTensor"):
         """The tensor compress_tensor took, on the device, in its dtype and shape."""
@@ -639,8 +720,12 @@ class Compressor:
         blocks = ct.blocks.to(dev)
         out = torch.empty(n, dtype=torch.uint8, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        off = self.unlz4_batch_typed_device(blocks.data_ptr(), ct.offsets, [e] * (len(ct.offsets) - 1), out.data_ptr(), n,
-                                            stream)
+        count = len(ct.offsets) - 1
+        if ct.filter == "bytes":
+            off = self.unlz4_batch_typed_device(blocks.data_ptr(), ct.offsets, [e] * count, out.data_ptr(), n, stream)
+        else:
+            off = self.unlz4_batch_filtered_device(blocks.data_ptr(), ct.offsets, [e] * count,
+                                                   self._filters(ct.filter, count), out.data_ptr(), n, stream)
         if off[-1] != n:
             raise _native.NativeError(f"the blocks decode to {off[-1]} bytes, the tensor has {n}")
         return out.view(ct.dtype).reshape(ct.shape)
@@ -810,19 +895,21 @@ def unlz4_batch(blocks) -> list[bytes]:
     return _ctx().unlz4_batch(blocks)
 
 
-def compress_batch_typed(items, elem_sizes=None, max_chain_length: int = MaxChainLength) -> list[bytes]:
-    """Every item split into its byte planes and compressed as one LZ4 block (Compressor.compress_batch_typed)."""
-    return _ctx().compress_batch_typed(items, elem_sizes, max_chain_length)
+def compress_batch_typed(items, elem_sizes=None, max_chain_length: int = MaxChainLength, filters=None) -> list[bytes]:
+    """Every item split into its byte planes (or, with filters, shuffled into its bit planes) and compressed as
+    one LZ4 block (Compressor.compress_batch_typed)."""
+    return _ctx().compress_batch_typed(items, elem_sizes, max_chain_length, filters)
 
 
-def unlz4_batch_typed(blocks, elem_sizes) -> list[bytes]:
-    """Every bare block decoded on its own and merged by its width (Compressor.unlz4_batch_typed)."""
-    return _ctx().unlz4_batch_typed(blocks, elem_sizes)
+def unlz4_batch_typed(blocks, elem_sizes, filters=None) -> list[bytes]:
+    """Every bare block decoded on its own and merged by its width and filter (Compressor.unlz4_batch_typed)."""
+    return _ctx().unlz4_batch_typed(blocks, elem_sizes, filters)
 
 
-def compress_tensor(t, chunk_bytes: int = 65536, max_chain_length: int = MaxChainLength) -> CompressedTensor:
+def compress_tensor(t, chunk_bytes: int = 65536, max_chain_length: int = MaxChainLength,
+                    filter: str = "bytes") -> CompressedTensor:
     """A tensor as typed blocks on the device (Compressor.compress_tensor)."""
-    return _ctx().compress_tensor(t, chunk_bytes, max_chain_length)
+    return _ctx().compress_tensor(t, chunk_bytes, max_chain_length, filter)
 
 
 def decompress_tensor(ct: CompressedTensor):

@@ -25,6 +25,8 @@ SZ4_ITEM_CAPACITY = 2
 SZ4_ITEM_ARG = 3
 SZ4_ITEM_QUEUE = 4
 SZ4_ITEM_INTERNAL = 5
+SZ4_FILTER_BYTES = 0
+SZ4_FILTER_BITS = 1
 SZ4_HEADER_SMALLZ4 = 0
 SZ4_HEADER_INDEPENDENT = 1
 SZ4_HEADER_NONE = 2
@@ -56,6 +58,12 @@ SIGNATURES = {
     "sz4_unlz4_batch_typed_device": (_i32, [_vp, _vp, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_uint8), _u64, _vp,
                                             _u64, ctypes.POINTER(_u64), _vp]),
     "sz4_last_merge_ms": (ctypes.c_float, [_vp]),
+    "sz4_compress_batch_filtered_device": (_i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_u32),
+                                                  ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8), _u64,
+                                                  _u32, _vp, _u64, ctypes.POINTER(_u64), _vp]),
+    "sz4_unlz4_batch_filtered_device": (_i32, [_vp, _vp, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_uint8),
+                                               ctypes.POINTER(ctypes.c_uint8), _u64, _vp, _u64, ctypes.POINTER(_u64),
+                                               _vp]),
     # decode queue: every table is a device pointer
     "sz4_dq_create": (_i32, [_vp, _u32, _u64, ctypes.POINTER(_vp)]),
     "sz4_dq_destroy": (None, [_vp]),

@@ -5,6 +5,9 @@
 //   k_batch_move    moves compressed blocks to their caller-order place when one piece ran as two
 //                   pipeline runs (items whose window fits the finders' LDS, and items whose does not)
 //   k_batch_merge   the inverse of the split, after the batch decoder (sz4_unlz4_batch_typed_device)
+//   k_batch_gather_bits, k_batch_merge_bits  the same two for a table that holds an item of SZ4_FILTER_BITS
+//                   (sz4_compress_batch_filtered_device, sz4_unlz4_batch_filtered_device): that item is shuffled
+//                   into its bit planes and back, 8 x 8 bit transposes in registers and a transpose across lanes
 // All are copies, bound by memory: 16-byte accesses on the aligned side, work cut by bytes.
 //   k_cq_items, k_cq_finish  the compress queue's ends (sz4_cq_enqueue): the caller's device pointer table
 //                   into the gather's item table, and the run's offsets and sizes out to the caller's tables
@@ -192,6 +195,45 @@ __device__ __forceinline__ uint4 plane_bytes(const uint8_t* __restrict__ src, ui
   return make_uint4((uint32_t)r[0], (uint32_t)(r[0] >> 32), (uint32_t)r[1], (uint32_t)(r[1] >> 32));
 }
 
+// The staged word of a byte-split item that the thread of item-relative offset `off` takes (`off` becomes that
+// word's offset; zeros from the item's end on).
+// Which word a thread takes is permuted inside the item: with wp = m / 16 whole words per plane, slot
+// j * E + k takes word k * wp + j (a bijection of the first E * wp words, the rest keep their place).  E
+// neighbouring lanes then build words of E different planes from the SAME 16 * E source bytes, so a
+// wave's load touches 64 / E spans and not 64, and every source line is fetched once per wave and
+// not by E waves far apart in the grid; the lanes of one plane still store 16 * 64 / E consecutive bytes.
+__device__ __forceinline__ uint4 split_word(const BatchTyped& it, uint64_t& off)
+{
+  const uint32_t E = it.elem, lg = __ffs(E) - 1, m = it.size >> lg;
+  if (E > 1) {
+    const uint64_t slot = off / 16, wp = m / 16;
+    if (slot < wp * E) off = 16 * ((slot & (E - 1)) * wp + (slot >> lg));
+  }
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (off < it.size) {
+    const uint32_t o = (uint32_t)off;
+    if (E == 1) {
+      uint64_t r0, r1;
+      gather_word(it.src, it.size, o, r0, r1);
+      v = make_uint4((uint32_t)r0, (uint32_t)(r0 >> 32), (uint32_t)r1, (uint32_t)(r1 >> 32));
+    } else {
+      const uint8_t* src = reinterpret_cast<const uint8_t*>(it.src);
+      uint32_t k = 0, e = m;  // e + 16 <= m: the word lies inside plane k, from element e on
+      if (o + 16 <= m * E) {
+        k = o / m;
+        e = o - k * m;
+      }
+      if (e + 16 <= m) {
+        const uint8_t* p = src + (uint64_t)e * E;
+        v = E == 2 ? plane_word<2>(p, k) : E == 4 ? plane_word<4>(p, k) : plane_word<8>(p, k);
+      } else {
+        v = plane_bytes(src, it.size, E, m, o);
+      }
+    }
+  }
+  return v;
+}
+
 // k_batch_gather with the split folded in: the same contract (every 16-byte word of the staging buffer is
 // written, zeros outside the items, work cut by staged bytes, any source alignment, no read outside the
 // aligned 16-byte source words that overlap an item).  One thread per staged word.  A word that lies inside one
@@ -210,40 +252,8 @@ __global__ __launch_bounds__(kGatherThreads) void k_batch_gather_planes(const Ba
     for (uint64_t w = w0 + threadIdx.x; w < w1; w += kGatherThreads) {
       const BatchTyped it = items[item_at(items, first, last + 1, 16 * w)];
       uint64_t off = 16 * w - it.start;  // item-relative offset of the word
-      const uint32_t E = it.elem, lg = __ffs(E) - 1, m = it.size >> lg;
-      // Which word a thread takes is permuted inside the item: with wp = m / 16 whole words per plane, slot
-      // j * E + k takes word k * wp + j (a bijection of the first E * wp words, the rest keep their place).  E
-      // neighbouring lanes then build words of E different planes from the SAME 16 * E source bytes, so a
-      // wave's load touches 64 / E spans and not 64, and every source line is fetched once per wave and
-      // not by E waves far apart in the grid; the lanes of one plane still store 16 * 64 / E consecutive bytes.
-      if (E > 1) {
-        const uint64_t slot = off / 16, wp = m / 16;
-        if (slot < wp * E) off = 16 * ((slot & (E - 1)) * wp + (slot >> lg));
-      }
-      const uint64_t at = it.start + off;
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (off < it.size) {
-        const uint32_t o = (uint32_t)off;
-        if (E == 1) {
-          uint64_t r0, r1;
-          gather_word(it.src, it.size, o, r0, r1);
-          v = make_uint4((uint32_t)r0, (uint32_t)(r0 >> 32), (uint32_t)r1, (uint32_t)(r1 >> 32));
-        } else {
-          const uint8_t* src = reinterpret_cast<const uint8_t*>(it.src);
-          uint32_t k = 0, e = m;  // e + 16 <= m: the word lies inside plane k, from element e on
-          if (o + 16 <= m * E) {
-            k = o / m;
-            e = o - k * m;
-          }
-          if (e + 16 <= m) {
-            const uint8_t* p = src + (uint64_t)e * E;
-            v = E == 2 ? plane_word<2>(p, k) : E == 4 ? plane_word<4>(p, k) : plane_word<8>(p, k);
-          } else {
-            v = plane_bytes(src, it.size, E, m, o);
-          }
-        }
-      }
-      *reinterpret_cast<uint4*>(staged + at) = v;
+      const uint4 v = split_word(it, off);
+      *reinterpret_cast<uint4*>(staged + it.start + off) = v;
     }
   }
 }
@@ -265,6 +275,59 @@ __device__ __forceinline__ uint4 merge_bytes(const BatchTyped* __restrict__ item
     else r1 |= x;
   }
   return make_uint4((uint32_t)r0, (uint32_t)(r0 >> 32), (uint32_t)r1, (uint32_t)(r1 >> 32));
+}
+
+// the bytes of output positions [lo, hi) of a byte-split item's merge: item idx (= it) holds position lo
+__device__ __forceinline__ uint4 merge_word(const BatchTyped* __restrict__ items, uint32_t idx, const BatchTyped& it,
+                                            const uint8_t* __restrict__ from, int64_t base, uint64_t lo, uint64_t hi)
+{
+  const uint32_t b = (uint32_t)(lo - it.start), E = it.elem, lg = __ffs(E) - 1, m = it.size >> lg;
+  const uint8_t* p = from + it.src;
+  uint4 v;
+  if (hi - lo == 16 && b + 16 <= it.size && E == 1) {
+    const Unaligned16 x = *reinterpret_cast<const Unaligned16*>(p + b);
+    v = make_uint4(x.x, x.y, x.z, x.w);
+  } else if (hi - lo == 16 && b + 16 <= (m << lg) && !(b & (E - 1))) {
+    const uint8_t* q = p + (b >> lg);
+    if (E == 2) {
+      const Unaligned8 x = *reinterpret_cast<const Unaligned8*>(q), y = *reinterpret_cast<const Unaligned8*>(q + m);
+      v = make_uint4(perm(y.x, x.x, 0x05010400u), perm(y.x, x.x, 0x07030602u), perm(y.y, x.y, 0x05010400u),
+                     perm(y.y, x.y, 0x07030602u));
+    } else if (E == 4) {
+      uint32_t x[4];
+#pragma unroll
+      for (uint32_t k = 0; k < 4; k++) x[k] = reinterpret_cast<const Unaligned4*>(q + (uint64_t)k * m)->x;
+      const uint32_t l0 = perm(x[1], x[0], 0x05010400u), l1 = perm(x[3], x[2], 0x05010400u);
+      const uint32_t h0 = perm(x[1], x[0], 0x07030602u), h1 = perm(x[3], x[2], 0x07030602u);
+      v = make_uint4(perm(l1, l0, 0x05040100u), perm(l1, l0, 0x07060302u), perm(h1, h0, 0x05040100u),
+                     perm(h1, h0, 0x07060302u));
+    } else {
+      uint32_t t[4];
+#pragma unroll
+      for (uint32_t k = 0; k < 4; k++)
+        t[k] = perm(reinterpret_cast<const Unaligned2*>(q + (uint64_t)(2 * k + 1) * m)->x,
+                    reinterpret_cast<const Unaligned2*>(q + (uint64_t)(2 * k) * m)->x, 0x05010400u);
+      v = make_uint4(perm(t[1], t[0], 0x05040100u), perm(t[3], t[2], 0x05040100u), perm(t[1], t[0], 0x07060302u),
+                     perm(t[3], t[2], 0x07060302u));
+    }
+  } else {
+    v = merge_bytes(items, idx, from, base, lo, hi);
+  }
+  return v;
+}
+
+// stores the bytes of positions [lo, hi) of the aligned word at `base`: whole, or byte by byte at the buffer's ends
+__device__ __forceinline__ void merge_store(uint8_t* __restrict__ to, uint4 v, int64_t base, uint64_t lo, uint64_t hi)
+{
+  if (hi - lo == 16) {
+    *reinterpret_cast<uint4*>(to + lo) = v;
+  } else {
+    const uint64_t x0 = v.x | ((uint64_t)v.y << 32), x1 = v.z | ((uint64_t)v.w << 32);
+    for (uint64_t pos = lo; pos < hi; pos++) {
+      const uint32_t i = (uint32_t)((int64_t)pos - base);
+      to[pos] = (uint8_t)((i < 8 ? x0 : x1) >> (8 * (i % 8)));
+    }
+  }
 }
 
 // The inverse of the split, from the batch decoder's scratch (item i's split bytes at from + src) to the
@@ -292,47 +355,307 @@ __global__ __launch_bounds__(kGatherThreads) void k_batch_merge(const BatchTyped
       const uint64_t hi = (uint64_t)(base + 16) < total ? (uint64_t)(base + 16) : total;
       const uint32_t idx = item_at(items, first, last + 1, lo);
       const BatchTyped it = items[idx];
-      const uint32_t b = (uint32_t)(lo - it.start), E = it.elem, lg = __ffs(E) - 1, m = it.size >> lg;
-      const uint8_t* p = from + it.src;
-      uint4 v;
-      if (hi - lo == 16 && b + 16 <= it.size && E == 1) {
-        const Unaligned16 x = *reinterpret_cast<const Unaligned16*>(p + b);
-        v = make_uint4(x.x, x.y, x.z, x.w);
-      } else if (hi - lo == 16 && b + 16 <= (m << lg) && !(b & (E - 1))) {
-        const uint8_t* q = p + (b >> lg);
-        if (E == 2) {
-          const Unaligned8 x = *reinterpret_cast<const Unaligned8*>(q), y = *reinterpret_cast<const Unaligned8*>(q + m);
-          v = make_uint4(perm(y.x, x.x, 0x05010400u), perm(y.x, x.x, 0x07030602u), perm(y.y, x.y, 0x05010400u),
-                         perm(y.y, x.y, 0x07030602u));
-        } else if (E == 4) {
-          uint32_t x[4];
-#pragma unroll
-          for (uint32_t k = 0; k < 4; k++) x[k] = reinterpret_cast<const Unaligned4*>(q + (uint64_t)k * m)->x;
-          const uint32_t l0 = perm(x[1], x[0], 0x05010400u), l1 = perm(x[3], x[2], 0x05010400u);
-          const uint32_t h0 = perm(x[1], x[0], 0x07030602u), h1 = perm(x[3], x[2], 0x07030602u);
-          v = make_uint4(perm(l1, l0, 0x05040100u), perm(l1, l0, 0x07060302u), perm(h1, h0, 0x05040100u),
-                         perm(h1, h0, 0x07060302u));
+      merge_store(to, merge_word(items, idx, it, from, base, lo, hi), base, lo, hi);
+    }
+  }
+}
+
+// ---- typed items: the bit-plane shuffle (SZ4_FILTER_BITS) and its inverse ------------------------------------
+// An item of `size` bytes and width E has m = size / E whole elements, of which g = m - m % 8 are shuffled into
+// 8 * E bit rows of G = g / 8 bytes: bit (e & 7) of shuffled byte (8 * k + b) * G + (e >> 3) is bit b of byte k of
+// element e.  The m % 8 left-over elements and the size % E tail bytes follow the rows unchanged.
+// BatchTyped::elem holds the width in its low byte and the filter above it.
+constexpr uint32_t kFilterShift = 8;
+__device__ __forceinline__ uint32_t item_width(const BatchTyped& it) { return it.elem & 0xFFu; }
+__device__ __forceinline__ bool item_bits(const BatchTyped& it) { return (it.elem >> kFilterShift) != 0; }
+
+// the transpose of an 8 x 8 bit matrix: bit c of byte r becomes bit r of byte c (three masked swap rounds)
+__device__ __forceinline__ uint64_t transpose8(uint64_t x)
+{
+  uint64_t t = (x ^ (x >> 7)) & 0x00AA00AA00AA00AAull;
+  x ^= t ^ (t << 7);
+  t = (x ^ (x >> 14)) & 0x0000CCCC0000CCCCull;
+  x ^= t ^ (t << 14);
+  t = (x ^ (x >> 28)) & 0x00000000F0F0F0F0ull;
+  x ^= t ^ (t << 28);
+  return x;
+}
+
+// one round of a transpose across lanes: the lanes whose `up` is clear keep (a0, a1) and give (b0, b1) to the
+// lane `mask` above them, from which they take its (a0, a1) into (b0, b1); the upper lanes the other way round.
+// Both lanes of a pair are in the same branch (the callers' fast paths hold for whole groups of lanes).
+__device__ __forceinline__ void lane_swap(uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1, bool up, int mask)
+{
+  const uint32_t r0 = (uint32_t)__shfl_xor((int)(up ? a0 : b0), mask), r1 = (uint32_t)__shfl_xor((int)(up ? a1 : b1), mask);
+  if (up) a0 = r0, a1 = r1;
+  else b0 = r0, b1 = r1;
+}
+
+// (x0, x1): byte k of elements 0..7 and 8..15.  Returns d[q] = the two bytes of bit row 2q (low half) and of
+// bit row 2q + 1 (high half) that these 16 elements make
+__device__ __forceinline__ uint4 bit_rows16(uint64_t x0, uint64_t x1)
+{
+  const uint64_t t0 = transpose8(x0), t1 = transpose8(x1);
+  const uint32_t l0 = (uint32_t)t0, h0 = (uint32_t)(t0 >> 32), l1 = (uint32_t)t1, h1 = (uint32_t)(t1 >> 32);
+  return make_uint4(perm(l1, l0, 0x05010400u), perm(l1, l0, 0x07030602u), perm(h1, h0, 0x05010400u),
+                    perm(h1, h0, 0x07030602u));
+}
+
+// bit b of each of the 8 bytes of x, byte t's into bit t
+__device__ __forceinline__ uint32_t bits8(uint64_t x, uint32_t b)
+{
+  return (uint32_t)((((x >> b) & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56);
+}
+
+// shuffled bytes [o, o + 16) of an item row byte by row byte (a word that straddles two rows, a row that does not
+// start at a multiple of 16, the left-over elements, the tail or the item's end; bytes from the end on read 0):
+// one division for the first byte, then the position is stepped.  At widths 1 and 2 two bytes of a row at a time
+// where the row has them -- bit b of byte k of 16 elements, 16 * E source bytes; at widths 4 and 8 that moved
+// more bytes through the L1 than eight byte loads cost, and ran slower -- and everything else bit by bit.
+__device__ __forceinline__ uint4 bits_bytes(const uint8_t* __restrict__ src, uint32_t size, uint32_t E, uint32_t G, uint32_t o)
+{
+  const uint32_t body = 8 * G * E;
+  uint32_t r = 0, c = 0;
+  if (o < body) {
+    r = o / G;
+    c = o - r * G;
+  }
+  uint64_t out[2] = {0, 0};
+#pragma unroll 1
+  for (uint32_t i = 0; i < 16;) {
+    const uint32_t pos = o + i;
+    if (pos >= size) break;
+    uint32_t v, step = 1;
+    if (pos < body) {
+      const uint32_t k = r >> 3, b = r & 7u;
+      const uint8_t* p = src + (uint64_t)(8 * c) * E;  // element 8c
+      if (E <= 2 && i < 15 && c + 1 < G) {             // the elements 8c .. 8c + 15 are inside the body
+        uint4 x;
+        if (E == 1) {
+          const Unaligned16 y = *reinterpret_cast<const Unaligned16*>(p);
+          x = make_uint4(y.x, y.y, y.z, y.w);
         } else {
-          uint32_t t[4];
+          x = plane_word<2>(p, k);
+        }
+        v = bits8(x.x | ((uint64_t)x.y << 32), b) | bits8(x.z | ((uint64_t)x.w << 32), b) << 8;
+        step = 2;
+      } else {
+        v = 0;
 #pragma unroll
-          for (uint32_t k = 0; k < 4; k++)
-            t[k] = perm(reinterpret_cast<const Unaligned2*>(q + (uint64_t)(2 * k + 1) * m)->x,
-                        reinterpret_cast<const Unaligned2*>(q + (uint64_t)(2 * k) * m)->x, 0x05010400u);
-          v = make_uint4(perm(t[1], t[0], 0x05040100u), perm(t[3], t[2], 0x05040100u), perm(t[1], t[0], 0x07060302u),
-                         perm(t[3], t[2], 0x07060302u));
-        }
-      } else {
-        v = merge_bytes(items, idx, from, base, lo, hi);
+        for (uint32_t t = 0; t < 8; t++) v |= ((p[t * E + k] >> b) & 1u) << t;
       }
-      if (hi - lo == 16) {
-        *reinterpret_cast<uint4*>(to + lo) = v;
+      c += step;
+      if (c == G) c = 0, r++;
+    } else {
+      v = src[pos];  // the left-over elements and the tail lie where they lay
+    }
+    out[i / 8] |= (uint64_t)(v & 0xFFu) << (8 * (i % 8));
+    if (step == 2) out[(i + 1) / 8] |= (uint64_t)(v >> 8) << (8 * ((i + 1) % 8));
+    i += step;
+  }
+  return make_uint4((uint32_t)out[0], (uint32_t)(out[0] >> 32), (uint32_t)out[1], (uint32_t)(out[1] >> 32));
+}
+
+// The staged word of a bit-shuffled item that the thread of item-relative offset `off` takes, as split_word.
+// With wr = G / 16 whole words per row when every row starts at a multiple of 16 (G % 16 == 0; otherwise 0),
+// the words of the item's 8 * E * wr row words are dealt to octets of lanes: octet (j, k) takes word j of the rows
+// 8k..8k + 7, lane i of it row 8k + i.  The octets of one j are neighbours, so E octets read the same 128 * E
+// source bytes.  Lane i loads byte k of the elements 128j + 16i .. + 15 (plane_word), transposes them as two
+// 8 x 8 bit blocks, and then holds two bytes for each of the eight rows; three lane_swap rounds (distances 4, 2,
+// 1: a transpose of an 8 x 8 matrix of 16-bit values held one row per lane) leave lane i with the sixteen bytes
+// of row 8k + i.  A staged item starts at a multiple of 64 bytes = 4 words, so the octets are lane-aligned only
+// after `pre` = 0 or 4 slots: those and the last octet's other slots take that octet's words bit by bit.
+__device__ __forceinline__ uint4 shuffle_word(const BatchTyped& it, uint64_t& off)
+{
+  const uint32_t E = item_width(it), lg = __ffs(E) - 1, m = it.size >> lg, G = m >> 3;
+  const uint32_t wr = G & 15u ? 0 : G >> 4, fast = wr << lg;  // octets in all
+  const uint32_t pre = (8 - ((uint32_t)(it.start >> 4) & 7u)) & 7u;
+  const uint32_t whole = fast - (pre && fast ? 1 : 0);  // lane-aligned octets
+  const uint64_t slot = off / 16;
+  uint32_t u = ~0u;
+  if (slot < 8ull * fast) {
+    u = (uint32_t)slot >= pre ? (uint32_t)slot - pre : (uint32_t)slot + 8 * fast - pre;
+    const uint32_t i = u & 7u, k = (u >> 3) & (E - 1), j = u >> (3 + lg);
+    off = 16ull * ((8 * k + i) * wr + j);
+  }
+  const uint8_t* src = reinterpret_cast<const uint8_t*>(it.src);
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if ((u >> 3) < whole) {
+    const uint32_t i = u & 7u, k = (u >> 3) & (E - 1), j = u >> (3 + lg);
+    const uint8_t* p = src + ((uint64_t)(128 * j + 16 * i) << lg);
+    uint4 x;
+    if (E == 1) {
+      const Unaligned16 y = *reinterpret_cast<const Unaligned16*>(p);
+      x = make_uint4(y.x, y.y, y.z, y.w);
+    } else {
+      x = E == 2 ? plane_word<2>(p, k) : E == 4 ? plane_word<4>(p, k) : plane_word<8>(p, k);
+    }
+    uint4 d = bit_rows16(x.x | ((uint64_t)x.y << 32), x.z | ((uint64_t)x.w << 32));
+    lane_swap(d.x, d.y, d.z, d.w, (i & 4u) != 0, 4);
+    lane_swap(d.x, d.z, d.y, d.w, (i & 2u) != 0, 2);
+    // distance 1 swaps the 16-bit halves: the lower lane keeps the low halves
+    {
+      const bool up = (i & 1u) != 0;
+      const uint32_t s0 = up ? perm(d.y, d.x, 0x05040100u) : perm(d.y, d.x, 0x07060302u);
+      const uint32_t s1 = up ? perm(d.w, d.z, 0x05040100u) : perm(d.w, d.z, 0x07060302u);
+      const uint32_t r0 = (uint32_t)__shfl_xor((int)s0, 1), r1 = (uint32_t)__shfl_xor((int)s1, 1);
+      if (up) {
+        d = make_uint4(perm(d.x, r0, 0x07060100u), perm(d.y, r0, 0x07060302u), perm(d.z, r1, 0x07060100u),
+                       perm(d.w, r1, 0x07060302u));
       } else {
-        const uint64_t x0 = v.x | ((uint64_t)v.y << 32), x1 = v.z | ((uint64_t)v.w << 32);
-        for (uint64_t pos = lo; pos < hi; pos++) {
-          const uint32_t i = (uint32_t)((int64_t)pos - base);
-          to[pos] = (uint8_t)((i < 8 ? x0 : x1) >> (8 * (i % 8)));
-        }
+        d = make_uint4(perm(r0, d.x, 0x05040100u), perm(r0, d.y, 0x07060100u), perm(r1, d.z, 0x05040100u),
+                       perm(r1, d.w, 0x07060100u));
       }
+    }
+    v = d;
+  } else if (off < it.size) {
+    v = bits_bytes(src, it.size, E, G, (uint32_t)off);
+  }
+  return v;
+}
+
+// k_batch_gather_planes for a run that has a bit-shuffled item: the same contract and the same tiling; an item
+// with the byte filter is staged by split_word, exactly as k_batch_gather_planes stages it.
+__global__ __launch_bounds__(kGatherThreads) void k_batch_gather_bits(const BatchTyped* __restrict__ items, uint32_t n,
+                                                                      uint8_t* __restrict__ staged, uint64_t words)
+{
+  const uint64_t tiles = (words + kGatherTile - 1) / kGatherTile;
+  for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const uint64_t w0 = tile * kGatherTile;
+    const uint64_t w1 = w0 + kGatherTile < words ? w0 + kGatherTile : words;
+    const uint32_t first = item_at(items, 0, n, 16 * w0);
+    const uint32_t last = item_at(items, first, n, 16 * (w1 - 1));
+    for (uint64_t w = w0 + threadIdx.x; w < w1; w += kGatherThreads) {
+      BatchTyped it = items[item_at(items, first, last + 1, 16 * w)];
+      uint64_t off = 16 * w - it.start;
+      uint4 v;
+      if (item_bits(it)) {
+        v = shuffle_word(it, off);
+      } else {
+        it.elem = item_width(it);
+        v = split_word(it, off);
+      }
+      *reinterpret_cast<uint4*>(staged + it.start + off) = v;
+    }
+  }
+}
+
+// the bytes of output positions [lo, hi) one by one, as merge_bytes, where items may be bit-shuffled
+__device__ __forceinline__ uint4 unshuffle_bytes(const BatchTyped* __restrict__ items, uint32_t idx, const uint8_t* __restrict__ from,
+                                                 int64_t base, uint64_t lo, uint64_t hi)
+{
+  BatchTyped it = items[idx];
+  uint64_t r0 = 0, r1 = 0;
+#pragma unroll 1
+  for (uint64_t pos = lo; pos < hi; pos++) {
+    while (pos >= it.start + it.size) it = items[++idx];
+    const uint32_t b = (uint32_t)(pos - it.start), E = item_width(it), lg = __ffs(E) - 1, m = it.size >> lg;
+    const uint8_t* p = from + it.src;
+    uint32_t v;
+    if (!item_bits(it)) {
+      v = p[b < (m << lg) ? (b & (E - 1)) * m + (b >> lg) : b];
+    } else if (b < ((m & ~7u) << lg)) {
+      const uint32_t G = m >> 3, e = b >> lg, k = b & (E - 1);
+      const uint8_t* q = p + (uint64_t)(8 * k) * G + (e >> 3);
+      v = 0;
+#pragma unroll
+      for (uint32_t t = 0; t < 8; t++) v |= ((q[(uint64_t)t * G] >> (e & 7u)) & 1u) << t;
+    } else {
+      v = p[b];
+    }
+    const uint32_t i = (uint32_t)((int64_t)pos - base);
+    const uint64_t x = (uint64_t)v << (8 * (i % 8));
+    if (i < 8) r0 |= x;
+    else r1 |= x;
+  }
+  return make_uint4((uint32_t)r0, (uint32_t)(r0 >> 32), (uint32_t)r1, (uint32_t)(r1 >> 32));
+}
+
+// The word at position lo = it.start + b of a bit-shuffled item's inverse.  The unit of the inverse is 8
+// consecutive elements, 8 * E output bytes: one byte from each of the 8 * E rows, an 8 x 8 bit transpose per
+// plane.  A unit is W = max(1, E / 2) output words, taken by W neighbouring lanes, so every lane loads 16 row
+// bytes whatever the width:
+//   E = 1  the word is two units: two bytes from each of the 8 rows
+//   E = 2  the word is one unit: one byte from each of the 16 rows
+//   E = 4, 8  lane q of the W loads the 16 rows of the planes 2q and 2q + 1, transposes them and then holds two
+//          bytes of each of the unit's 8 elements; one (E = 4) or two (E = 8) lane_swap rounds -- a transpose of a
+//          W x W matrix of 8 / W elements x 2 bytes -- leave it with all the bytes of its own 8 / W elements
+// The fast path needs the unit to start at an aligned word that is the first of W lanes (b a multiple of 8 * E
+// for the first word, of 8 for E = 1; word index a multiple of W); everything else goes bit by bit.
+__device__ __forceinline__ uint4 unshuffle_word(const BatchTyped* __restrict__ items, uint32_t idx, const BatchTyped& it,
+                                                const uint8_t* __restrict__ from, int64_t base, uint64_t lo, uint64_t hi,
+                                                uint64_t w)
+{
+  const uint32_t b = (uint32_t)(lo - it.start), E = item_width(it), lg = __ffs(E) - 1, m = it.size >> lg, G = m >> 3;
+  const uint32_t W = E > 2 ? E >> 1 : 1, q = (uint32_t)w & (W - 1), b0 = b - 16 * q;  // the unit's first word
+  const uint32_t need = E == 1 ? 7u : 8 * E - 1;
+  const bool fast = hi - lo == 16 && b >= 16 * q && !(b0 & need) && b0 + 16 * W <= 8 * G * E;
+  if (!fast) return unshuffle_bytes(items, idx, from, base, lo, hi);
+  const uint8_t* p = from + it.src;
+  if (E == 1) {
+    p += b >> 3;
+    uint64_t x0 = 0, x1 = 0;
+#pragma unroll
+    for (uint32_t t = 0; t < 8; t++) {
+      const uint32_t y = reinterpret_cast<const Unaligned2*>(p + (uint64_t)t * G)->x;
+      x0 |= (uint64_t)(y & 0xFFu) << (8 * t);
+      x1 |= (uint64_t)(y >> 8) << (8 * t);
+    }
+    x0 = transpose8(x0), x1 = transpose8(x1);
+    return make_uint4((uint32_t)x0, (uint32_t)(x0 >> 32), (uint32_t)x1, (uint32_t)(x1 >> 32));
+  }
+  p += (uint64_t)(16 * q) * G + ((b0 >> lg) >> 3);
+  uint64_t x0 = 0, x1 = 0;
+#pragma unroll
+  for (uint32_t t = 0; t < 8; t++) {
+    x0 |= (uint64_t)p[(uint64_t)t * G] << (8 * t);
+    x1 |= (uint64_t)p[(uint64_t)(8 + t) * G] << (8 * t);
+  }
+  // d[n]: the bytes 2q, 2q + 1 of the elements 2n (low half) and 2n + 1 (high half)
+  uint4 d = bit_rows16(x0, x1);
+  if (E == 2) return d;
+  if (E == 4) {
+    lane_swap(d.x, d.y, d.z, d.w, q != 0, 1);
+    // lane 0: (x, y) its own bytes 0, 1 of elements 0..3 and (z, w) bytes 2, 3; lane 1 the same of elements 4..7
+    return make_uint4(perm(d.z, d.x, 0x05040100u), perm(d.z, d.x, 0x07060302u), perm(d.w, d.y, 0x05040100u),
+                      perm(d.w, d.y, 0x07060302u));
+  }
+  lane_swap(d.x, d.y, d.z, d.w, (q & 2u) != 0, 2);
+  lane_swap(d.x, d.z, d.y, d.w, (q & 1u) != 0, 1);
+  // d[n]: the bytes 2n, 2n + 1 of the elements 2q (low half) and 2q + 1 (high half)
+  return make_uint4(perm(d.y, d.x, 0x05040100u), perm(d.w, d.z, 0x05040100u), perm(d.y, d.x, 0x07060302u),
+                    perm(d.w, d.z, 0x07060302u));
+}
+
+// k_batch_merge for a call that has a bit-shuffled item: the same contract and the same tiling; a word that
+// starts in an item with the byte filter is merged by merge_word where that item holds all of it.
+__global__ __launch_bounds__(kGatherThreads) void k_batch_merge_bits(const BatchTyped* __restrict__ items, uint32_t n,
+                                                                     const uint8_t* __restrict__ from, uint8_t* __restrict__ to,
+                                                                     uint64_t total, uint64_t words)
+{
+  const int64_t a0 = (int64_t)(reinterpret_cast<uintptr_t>(to) & 15u);
+  const uint64_t tiles = (words + kGatherTile - 1) / kGatherTile;
+  for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const uint64_t w0 = tile * kGatherTile;
+    const uint64_t w1 = w0 + kGatherTile < words ? w0 + kGatherTile : words;
+    const uint32_t first = item_at(items, 0, n, w0 ? 16 * w0 - a0 : 0);
+    const uint32_t last = item_at(items, first, n, total - 1 < 16 * w1 - a0 - 1 ? total - 1 : 16 * w1 - a0 - 1);
+    for (uint64_t w = w0 + threadIdx.x; w < w1; w += kGatherThreads) {
+      const int64_t base = (int64_t)(16 * w) - a0;
+      const uint64_t lo = base < 0 ? 0 : (uint64_t)base;
+      const uint64_t hi = (uint64_t)(base + 16) < total ? (uint64_t)(base + 16) : total;
+      const uint32_t idx = item_at(items, first, last + 1, lo);
+      BatchTyped it = items[idx];
+      uint4 v;
+      if (item_bits(it)) {
+        v = unshuffle_word(items, idx, it, from, base, lo, hi, w);
+      } else if (hi <= it.start + it.size) {
+        it.elem = item_width(it);
+        v = merge_word(items, idx, it, from, base, lo, hi);
+      } else {
+        v = unshuffle_bytes(items, idx, from, base, lo, hi);
+      }
+      merge_store(to, v, base, lo, hi);
     }
   }
 }
@@ -505,12 +828,31 @@ void launch_batch_gather_planes(const BatchTyped* items, uint32_t n, uint8_t* st
                      s, items, n, staged, words);
 }
 
+void launch_batch_gather_bits(const BatchTyped* items, uint32_t n, uint8_t* staged, uint64_t stagedBytes, hipStream_t s)
+{
+  static_assert(kFilterShift == kBatchFilterShift, "the host's encoding of BatchTyped::elem");
+  const uint64_t words = stagedBytes / 16;
+  if (!n || !words) return;
+  const uint64_t tiles = (words + kGatherTile - 1) / kGatherTile;
+  hipLaunchKernelGGL(k_batch_gather_bits, dim3((uint32_t)(tiles < kGatherGrid ? tiles : kGatherGrid)), dim3(kGatherThreads), 0,
+                     s, items, n, staged, words);
+}
+
 void launch_batch_merge(const BatchTyped* items, uint32_t n, const uint8_t* from, uint8_t* to, uint64_t total, hipStream_t s)
 {
   if (!n || !total) return;
   const uint64_t words = ((reinterpret_cast<uintptr_t>(to) & 15u) + total + 15) / 16;
   const uint64_t tiles = (words + kGatherTile - 1) / kGatherTile;
   hipLaunchKernelGGL(k_batch_merge, dim3((uint32_t)(tiles < kGatherGrid ? tiles : kGatherGrid)), dim3(kGatherThreads), 0, s,
+                     items, n, from, to, total, words);
+}
+
+void launch_batch_merge_bits(const BatchTyped* items, uint32_t n, const uint8_t* from, uint8_t* to, uint64_t total, hipStream_t s)
+{
+  if (!n || !total) return;
+  const uint64_t words = ((reinterpret_cast<uintptr_t>(to) & 15u) + total + 15) / 16;
+  const uint64_t tiles = (words + kGatherTile - 1) / kGatherTile;
+  hipLaunchKernelGGL(k_batch_merge_bits, dim3((uint32_t)(tiles < kGatherGrid ? tiles : kGatherGrid)), dim3(kGatherThreads), 0, s,
                      items, n, from, to, total, words);
 }
 

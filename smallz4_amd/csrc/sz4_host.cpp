@@ -1145,12 +1145,17 @@ bool batch_fits_lds(uint64_t size) { return (size + 8 + 3) / 4 * 4 <= find_lds_b
 // top bit = stored); the blocks lie back to back in idx order.  elems (null: every item as it is) holds the
 // items' element widths: a run with an item wider than 1 is staged by k_batch_gather_planes, which splits
 // every item into its byte planes on the way (the plan is the same: a split item has its item's size).
+// filters (null: SZ4_FILTER_BYTES throughout) holds the items' filters: a run with an item of SZ4_FILTER_BITS, of
+// any width, is staged by k_batch_gather_bits.
 int batch_run(sz4_ctx* c, const std::vector<uint64_t>& idx, const void* const* ptrs, const uint32_t* sizes,
-              const uint8_t* elems, uint32_t maxChain, uint8_t* out, uint64_t outCap, std::vector<uint32_t>& bytes, hipStream_t s)
+              const uint8_t* elems, const uint8_t* filters, uint32_t maxChain, uint8_t* out, uint64_t outCap,
+              std::vector<uint32_t>& bytes, hipStream_t s)
 {
   const uint32_t nb = (uint32_t)idx.size();
-  bool planes = false;
+  bool planes = false, bits = false;
   for (uint32_t k = 0; elems && k < nb; k++) planes |= elems[idx[k]] > 1;
+  for (uint32_t k = 0; filters && k < nb; k++) bits |= filters[idx[k]] == SZ4_FILTER_BITS;
+  planes |= bits;
   std::vector<BatchItem> items(planes ? 0 : nb);
   std::vector<BatchTyped> typed(planes ? nb : 0);
   std::vector<uint64_t> runSizes(nb);
@@ -1158,7 +1163,9 @@ int batch_run(sz4_ctx* c, const std::vector<uint64_t>& idx, const void* const* p
   const uint64_t stagedBytes = c->pipe.plan.build_ragged(runSizes) + kPad;
   for (uint32_t k = 0; k < nb; k++) {
     const uint64_t at = c->pipe.plan.blocks[k].start, n = runSizes[k];
-    if (planes) typed[k] = BatchTyped{(uint64_t)(uintptr_t)ptrs[idx[k]], at, (uint32_t)n, elems[idx[k]]};
+    if (planes)
+      typed[k] = BatchTyped{(uint64_t)(uintptr_t)ptrs[idx[k]], at, (uint32_t)n,
+                            elems[idx[k]] | (bits ? (uint32_t)filters[idx[k]] << kBatchFilterShift : 0u)};
     else items[k] = BatchItem{(uint64_t)(uintptr_t)ptrs[idx[k]], at, n};
   }
   hipError_t e = hipSuccess;
@@ -1171,7 +1178,8 @@ int batch_run(sz4_ctx* c, const std::vector<uint64_t>& idx, const void* const* p
                           hipMemcpyHostToDevice, s)))
     return c->fail(SZ4_E_DEVICE, "upload items", e);
   if (c->timing) hipEventRecord(c->evGather[0], s);
-  if (planes) launch_batch_gather_planes(c->pipe.batchItems.as<BatchTyped>(), nb, c->pipe.staged.as<uint8_t>(), stagedBytes, s);
+  if (bits) launch_batch_gather_bits(c->pipe.batchItems.as<BatchTyped>(), nb, c->pipe.staged.as<uint8_t>(), stagedBytes, s);
+  else if (planes) launch_batch_gather_planes(c->pipe.batchItems.as<BatchTyped>(), nb, c->pipe.staged.as<uint8_t>(), stagedBytes, s);
   else launch_batch_gather(c->pipe.batchItems.as<BatchItem>(), nb, c->pipe.staged.as<uint8_t>(), stagedBytes, s);
   if (c->timing) hipEventRecord(c->evGather[1], s);
   uint64_t size = 0;
@@ -1193,7 +1201,7 @@ int batch_run(sz4_ctx* c, const std::vector<uint64_t>& idx, const void* const* p
 // its caller-order offset -- no payload byte passes through the host.  ext[i] receives item i's bytes in
 // d_out (0 for an empty item); the piece occupies d_out[pos, pos + sum of ext).
 int batch_piece(sz4_ctx* c, uint64_t i0, uint64_t i1, const void* const* ptrs, const uint32_t* sizes, const uint8_t* elems,
-                uint32_t maxChain, uint8_t* dOut, uint64_t pos, uint32_t* ext, float* stageSum, hipStream_t s)
+                const uint8_t* filters, uint32_t maxChain, uint8_t* dOut, uint64_t pos, uint32_t* ext, float* stageSum, hipStream_t s)
 {
   std::vector<uint64_t> run[2];
   uint64_t bound[2] = {0, 0};
@@ -1211,7 +1219,7 @@ int batch_piece(sz4_ctx* c, uint64_t i0, uint64_t i1, const void* const* ptrs, c
   if (run[0].empty() || run[1].empty()) {
     const int k = run[0].empty() ? 1 : 0;
     if (run[k].empty()) return SZ4_OK;
-    if (int r = batch_run(c, run[k], ptrs, sizes, elems, maxChain, dOut + pos, bound[k], bytes[k], s)) return r;
+    if (int r = batch_run(c, run[k], ptrs, sizes, elems, filters, maxChain, dOut + pos, bound[k], bytes[k], s)) return r;
     add_stages();
     for (size_t j = 0; j < run[k].size(); j++) ext[run[k][j]] = bytes[k][j] & 0x7FFFFFFFu;
     return SZ4_OK;
@@ -1220,7 +1228,7 @@ int batch_piece(sz4_ctx* c, uint64_t i0, uint64_t i1, const void* const* ptrs, c
   if ((e = c->batchTmp.reserve(bound[0] + bound[1] + 64))) return c->fail(SZ4_E_NOMEM, "batch staging", e);
   const uint64_t base[2] = {0, bound[0]};
   for (int k = 0; k < 2; k++) {
-    if (int r = batch_run(c, run[k], ptrs, sizes, elems, maxChain, c->batchTmp.as<uint8_t>() + base[k], bound[k], bytes[k],
+    if (int r = batch_run(c, run[k], ptrs, sizes, elems, filters, maxChain, c->batchTmp.as<uint8_t>() + base[k], bound[k], bytes[k],
                           s))
       return r;
     add_stages();
@@ -1495,14 +1503,16 @@ uint64_t sz4_batch_bound(const uint32_t* sizes, uint64_t count)
   return b;
 }
 
-// sz4_compress_batch_device (elem_sizes null) and sz4_compress_batch_typed_device
+// sz4_compress_batch_device (elem_sizes null), sz4_compress_batch_typed_device (filters null) and
+// sz4_compress_batch_filtered_device
 static int compress_batch(sz4_ctx* c, const void* const* in_ptrs, const uint32_t* in_sizes, const uint8_t* elem_sizes,
-                          uint64_t count, uint32_t max_chain, void* d_out, uint64_t out_cap, uint64_t* out_offsets, void* stream)
+                          const uint8_t* filters, uint64_t count, uint32_t max_chain, void* d_out, uint64_t out_cap,
+                          uint64_t* out_offsets, void* stream)
 {
   if (!c || !out_offsets || (count && (!in_ptrs || !in_sizes)) || max_chain > 65535)
     return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
   c->begin_call();
-  bool typed = false;
+  bool typed = false, bits = false;
   for (uint64_t i = 0; i < count; i++) {
     if (in_sizes[i] > kBlockMax) return c->fail(SZ4_E_ARG, "item larger than 4 MiB");
     if (in_sizes[i] && !in_ptrs[i]) return c->fail(SZ4_E_ARG, "null item pointer");
@@ -1511,8 +1521,13 @@ static int compress_batch(sz4_ctx* c, const void* const* in_ptrs, const uint32_t
       if (e != 1 && e != 2 && e != 4 && e != 8) return c->fail(SZ4_E_ARG, "element width is not 1, 2, 4 or 8");
       typed |= e > 1;
     }
+    if (filters) {
+      if (filters[i] != SZ4_FILTER_BYTES && filters[i] != SZ4_FILTER_BITS) return c->fail(SZ4_E_ARG, "unknown filter");
+      bits |= filters[i] == SZ4_FILTER_BITS;
+    }
   }
-  if (!typed) elem_sizes = nullptr;  // widths of 1 throughout: the plain call
+  if (!bits) filters = nullptr;                // the byte filter throughout: the typed call
+  if (!typed && !bits) elem_sizes = nullptr;  // and widths of 1 throughout: the plain call
   // the kernels write the blocks in place: refuse a buffer that could be overrun
   const uint64_t bound = sz4_batch_bound(in_sizes, count);
   if (out_cap < bound) return c->fail(SZ4_E_CAPACITY, "out_cap < sz4_batch_bound(sizes, count)");
@@ -1542,8 +1557,8 @@ static int compress_batch(sz4_ctx* c, const void* const* in_ptrs, const uint32_t
       staged += st;
       blocks++;
     }
-    const int r =
-        batch_piece(c, i, j, in_ptrs, in_sizes, elem_sizes, max_chain, (uint8_t*)d_out, pos, c->hostBytes.data(), stageSum, s);
+    const int r = batch_piece(c, i, j, in_ptrs, in_sizes, elem_sizes, filters, max_chain, (uint8_t*)d_out, pos,
+                              c->hostBytes.data(), stageSum, s);
     if (r == SZ4_E_NOMEM && blocks > 1 && piece > kPieceFloor) {
       piece = std::max<uint64_t>(kPieceFloor, piece / 2);
       continue;  // the same items again, in smaller pieces
@@ -1565,7 +1580,7 @@ static int compress_batch(sz4_ctx* c, const void* const* in_ptrs, const uint32_t
 int sz4_compress_batch_device(sz4_ctx* c, const void* const* in_ptrs, const uint32_t* in_sizes, uint64_t count,
                               uint32_t max_chain, void* d_out, uint64_t out_cap, uint64_t* out_offsets, void* stream)
 {
-  return compress_batch(c, in_ptrs, in_sizes, nullptr, count, max_chain, d_out, out_cap, out_offsets, stream);
+  return compress_batch(c, in_ptrs, in_sizes, nullptr, nullptr, count, max_chain, d_out, out_cap, out_offsets, stream);
 }
 
 int sz4_compress_batch_typed_device(sz4_ctx* c, const void* const* in_ptrs, const uint32_t* in_sizes, const uint8_t* elem_sizes,
@@ -1573,7 +1588,15 @@ int sz4_compress_batch_typed_device(sz4_ctx* c, const void* const* in_ptrs, cons
                                     void* stream)
 {
   if (count && !elem_sizes) return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
-  return compress_batch(c, in_ptrs, in_sizes, elem_sizes, count, max_chain, d_out, out_cap, out_offsets, stream);
+  return compress_batch(c, in_ptrs, in_sizes, elem_sizes, nullptr, count, max_chain, d_out, out_cap, out_offsets, stream);
+}
+
+int sz4_compress_batch_filtered_device(sz4_ctx* c, const void* const* in_ptrs, const uint32_t* in_sizes, const uint8_t* elem_sizes,
+                                       const uint8_t* filters, uint64_t count, uint32_t max_chain, void* d_out, uint64_t out_cap,
+                                       uint64_t* out_offsets, void* stream)
+{
+  if (count && !elem_sizes) return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
+  return compress_batch(c, in_ptrs, in_sizes, elem_sizes, filters, count, max_chain, d_out, out_cap, out_offsets, stream);
 }
 
 float sz4_last_gather_ms(sz4_ctx* c) { return c ? c->gatherMs : 0.0f; }
@@ -1581,20 +1604,27 @@ float sz4_last_gather_ms(sz4_ctx* c) { return c ? c->gatherMs : 0.0f; }
 float sz4_last_merge_ms(sz4_ctx* c) { return c ? c->mergeMs : 0.0f; }
 
 // sz4_unlz4_batch_device (elem_sizes null: the blocks decode straight into d_out) and
-// sz4_unlz4_batch_typed_device (they decode into unPlanes, and k_batch_merge writes d_out)
-static int unlz4_batch(sz4_ctx* c, const void* d_blocks, const uint64_t* offsets, const uint8_t* elem_sizes, uint64_t count,
+// sz4_unlz4_batch_typed_device (they decode into unPlanes, and k_batch_merge writes d_out; filters null) and
+// sz4_unlz4_batch_filtered_device (the same, with k_batch_merge_bits where an item has SZ4_FILTER_BITS)
+static int unlz4_batch(sz4_ctx* c, const void* d_blocks, const uint64_t* offsets, const uint8_t* elem_sizes,
+                       const uint8_t* filters, uint64_t count,
                        void* d_out, uint64_t out_cap, uint64_t* out_offsets, void* stream)
 {
   if (!c || !out_offsets || (count && !offsets)) return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
   c->begin_call();
   c->mergeMs = 0;
-  bool typed = false;
+  bool typed = false, bits = false;
   for (uint64_t i = 0; elem_sizes && i < count; i++) {
     const uint8_t e = elem_sizes[i];
     if (e != 1 && e != 2 && e != 4 && e != 8) return c->fail(SZ4_E_ARG, "element width is not 1, 2, 4 or 8");
     typed |= e > 1;
   }
-  if (!typed) elem_sizes = nullptr;  // widths of 1 throughout: the plain call
+  for (uint64_t i = 0; filters && i < count; i++) {
+    if (filters[i] != SZ4_FILTER_BYTES && filters[i] != SZ4_FILTER_BITS) return c->fail(SZ4_E_ARG, "unknown filter");
+    bits |= filters[i] == SZ4_FILTER_BITS;
+  }
+  if (!bits) filters = nullptr;                // the byte filter throughout: the typed call
+  if (!typed && !bits) elem_sizes = nullptr;  // and widths of 1 throughout: the plain call
   DeviceGuard guard(c->device);
   try {
   hipStream_t s = (hipStream_t)stream;
@@ -1656,7 +1686,9 @@ static int unlz4_batch(sz4_ctx* c, const void* d_blocks, const uint64_t* offsets
   std::vector<BatchTyped> merge;
   if (elem_sizes) {
     for (uint32_t b = 0; b < nb; b++)
-      if (c->hUn[b].size) merge.push_back(BatchTyped{c->hUn[b].dst, c->hUn[b].dst, (uint32_t)c->hUn[b].size, elem_sizes[item[b]]});
+      if (c->hUn[b].size)
+        merge.push_back(BatchTyped{c->hUn[b].dst, c->hUn[b].dst, (uint32_t)c->hUn[b].size,
+                                   elem_sizes[item[b]] | (bits ? (uint32_t)filters[item[b]] << kBatchFilterShift : 0u)});
     if ((e = c->unPlanes.reserve(w + 64)) || (e = c->mergeItems.reserve(merge.size() * sizeof(BatchTyped) + 64)))
       return c->fail(SZ4_E_NOMEM, "typed decoder scratch", e);
     target = c->unPlanes.as<uint8_t>();
@@ -1669,7 +1701,8 @@ static int unlz4_batch(sz4_ctx* c, const void* d_blocks, const uint64_t* offsets
   launch_unlz4_blocks_indep(f, n, c->unBlk.as<UnBlock>(), nb, c->unSeq.as<uint4>(), target, status, s);
   if (elem_sizes) {
     if (c->timing) hipEventRecord(c->evMerge[0], s);
-    launch_batch_merge(c->mergeItems.as<BatchTyped>(), (uint32_t)merge.size(), target, (uint8_t*)d_out, w, s);
+    if (bits) launch_batch_merge_bits(c->mergeItems.as<BatchTyped>(), (uint32_t)merge.size(), target, (uint8_t*)d_out, w, s);
+    else launch_batch_merge(c->mergeItems.as<BatchTyped>(), (uint32_t)merge.size(), target, (uint8_t*)d_out, w, s);
     if (c->timing) hipEventRecord(c->evMerge[1], s);
   }
   if ((e = hipGetLastError()) || (e = hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, s)) ||
@@ -1686,14 +1719,22 @@ static int unlz4_batch(sz4_ctx* c, const void* d_blocks, const uint64_t* offsets
 int sz4_unlz4_batch_device(sz4_ctx* c, const void* d_blocks, const uint64_t* offsets, uint64_t count, void* d_out,
                            uint64_t out_cap, uint64_t* out_offsets, void* stream)
 {
-  return unlz4_batch(c, d_blocks, offsets, nullptr, count, d_out, out_cap, out_offsets, stream);
+  return unlz4_batch(c, d_blocks, offsets, nullptr, nullptr, count, d_out, out_cap, out_offsets, stream);
 }
 
 int sz4_unlz4_batch_typed_device(sz4_ctx* c, const void* d_blocks, const uint64_t* offsets, const uint8_t* elem_sizes,
                                  uint64_t count, void* d_out, uint64_t out_cap, uint64_t* out_offsets, void* stream)
 {
   if (count && !elem_sizes) return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
-  return unlz4_batch(c, d_blocks, offsets, elem_sizes, count, d_out, out_cap, out_offsets, stream);
+  return unlz4_batch(c, d_blocks, offsets, elem_sizes, nullptr, count, d_out, out_cap, out_offsets, stream);
+}
+
+int sz4_unlz4_batch_filtered_device(sz4_ctx* c, const void* d_blocks, const uint64_t* offsets, const uint8_t* elem_sizes,
+                                    const uint8_t* filters, uint64_t count, void* d_out, uint64_t out_cap, uint64_t* out_offsets,
+                                    void* stream)
+{
+  if (count && !elem_sizes) return c ? c->fail(SZ4_E_ARG, "bad argument") : SZ4_E_ARG;
+  return unlz4_batch(c, d_blocks, offsets, elem_sizes, filters, count, d_out, out_cap, out_offsets, stream);
 }
 
 // ---- decode queue: everything an enqueue needs, reserved once on the context's budget and held -----------

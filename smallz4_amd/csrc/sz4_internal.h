@@ -321,6 +321,12 @@ void launch_batch_gather_planes(const BatchTyped* items, uint32_t n, uint8_t* st
 // the inverse: to[start, start + size) = merge(from[src, src + size), elem) for every item; the items are
 // non-empty, ascending and back to back in `to` (starts are running sums from 0 to `total`); `to` has any alignment
 void launch_batch_merge(const BatchTyped* items, uint32_t n, const uint8_t* from, uint8_t* to, uint64_t total, hipStream_t s);
+// filtered items (sz4_compress_batch_filtered_device / sz4_unlz4_batch_filtered_device): a table with an item
+// of SZ4_FILTER_BITS holds (filter << kBatchFilterShift) | width in `elem` and goes to these two, which shuffle
+// such an item into its bit planes (and back) and treat every other item as the two above do
+constexpr uint32_t kBatchFilterShift = 8;
+void launch_batch_gather_bits(const BatchTyped* items, uint32_t n, uint8_t* staged, uint64_t stagedBytes, hipStream_t s);
+void launch_batch_merge_bits(const BatchTyped* items, uint32_t n, const uint8_t* from, uint8_t* to, uint64_t total, hipStream_t s);
 // moves compressed blocks to their caller-order place: entry k copies len bytes from `from + src` to `to + dst`
 // (the host cuts long blocks into entries of at most kBatchMoveMax bytes, so the work is balanced by bytes)
 constexpr uint64_t kBatchMoveMax = 65536;

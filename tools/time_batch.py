@@ -9,7 +9,8 @@ whole sequence runs --rounds times so that drift shows; rates are means over all
 min..max spread, the stage split and the gather time are the last call's.  The batch legs' times include
 the Python binding's marshalling of the pointer and size lists.
     python3 tools/time_batch.py [--mb 100] [--reps 5] [--rounds 2] [--chain 65535]
-With --elem 2,4,8 it times the typed batch API's two kernels instead (see typed() below)."""
+With --elem 2,4,8 it times the typed batch API's two kernels instead (see typed() below); with --filter bits
+beside it, the bit-plane shuffle's gather and merge (the filtered calls, every item SZ4_FILTER_BITS)."""
 import argparse
 import os
 import random
@@ -33,10 +34,12 @@ def typed(a):
     """--elem: the split gather (k_batch_gather_planes) against the plain gather on the same items, and the
     merge (k_batch_merge) against a device-to-device copy of the same bytes.  Item sets: 1526 items of
     64 KiB, 10 000 items of 200 bytes to 4 KiB, and those cut down to whole elements; medians of the device
-    times over reps x rounds calls."""
+    times over reps x rounds calls.  --filter bits: the same loop through the filtered calls, every item (width 1
+    too) shuffled into its bit planes (k_batch_gather_bits, k_batch_merge_bits); the plain gather stays the base."""
     import numpy as np
     dev = torch.device("cuda:0")
     widths = [1] + [int(x) for x in a.elem.split(",") if int(x) != 1]
+    bits = a.filter == "bits"
     rng = random.Random(9)
     small = [rng.randrange(200, 4097) for _ in range(10000)]
     # the third set is the second with whole elements only: every item then lands at a multiple of its width
@@ -69,23 +72,27 @@ def typed(a):
         print(f"{label}: {n} bytes, device-to-device copy {copy_ms:.4f} ms [{min(copies[1:]):.4f} .. {max(copies[1:]):.4f}]",
               flush=True)
         base = None
-        for E in widths:
-            elems = [E] * len(sizes)
+        for E in ([0] if bits else []) + widths:  # width 0: the plain gather, the base of a --filter bits run
+            elems = [E or 1] * len(sizes)
+            filters = [smallz4_amd.FILTERS["bits" if bits and E else "bytes"]] * len(sizes)
             gather, merge = [], []
             for rep in range(a.reps * a.rounds + 1):
-                off = comp.compress_batch_typed_device(ptrs, sizes, elems, out.data_ptr(), cap, a.chain)
+                off = comp.compress_batch_filtered_device(ptrs, sizes, elems, filters, out.data_ptr(), cap, a.chain)
                 g_ms = comp.last_gather_ms()
-                got = comp.unlz4_batch_typed_device(out.data_ptr(), off, elems, dec.data_ptr(), n)
+                got = comp.unlz4_batch_filtered_device(out.data_ptr(), off, elems, filters, dec.data_ptr(), n)
                 m_ms = comp.last_merge_ms()
                 assert got[-1] == n and torch.equal(dec, t_in), (label, E)
                 if rep:
                     gather.append(g_ms)
                     merge.append(m_ms)
             g_ms, m_ms = median(gather), median(merge)
-            base = g_ms if E == 1 else base
-            line = (f"  E={E}: gather {g_ms:.4f} ms [{min(gather):.4f} .. {max(gather):.4f}] ({g_ms / base:.2f}x the plain "
+            base = g_ms if E == (0 if bits else 1) else base
+            if not E:
+                print(f"  plain gather {g_ms:.4f} ms [{min(gather):.4f} .. {max(gather):.4f}]", flush=True)
+                continue
+            line = (f"  E={E}{' bits' if bits else ''}: gather {g_ms:.4f} ms [{min(gather):.4f} .. {max(gather):.4f}] ({g_ms / base:.2f}x the plain "
                     f"gather), {off[-1]} bytes out")
-            if E > 1:
+            if E > 1 or bits:
                 line += f", merge {m_ms:.4f} ms [{min(merge):.4f} .. {max(merge):.4f}] ({m_ms / copy_ms:.2f}x the copy)"
             print(line, flush=True)
 
@@ -97,6 +104,8 @@ def main():
     ap.add_argument("--chain", type=int, default=65535)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--elem", default="", help="element widths, e.g. 2,4,8: time the typed gather and merge instead")
+    ap.add_argument("--filter", default="bytes", choices=["bytes", "bits"],
+                    help="with --elem: bits times the bit-plane shuffle's gather and merge")
     a = ap.parse_args()
     if a.elem:
         return typed(a)
