@@ -68,7 +68,9 @@ uint64_t sz4_bound(uint64_t n, uint32_t block_size);
  * sz4_set_batch_chunk bytes (by default 448 MiB, split into equal pieces, and capped so that the scratch -- under 50 bytes
  * per piece byte -- takes at most a quarter of the device memory the context could use now;
  * under a sz4_set_device_limit bound about 1/64 of the bound).  A piece whose scratch cannot
- * be allocated is halved and retried, down to 16 MiB, before SZ4_E_NOMEM.
+ * be allocated is halved and retried, down to 16 MiB, before SZ4_E_NOMEM: the context first releases the
+ * device buffers it holds (all but a live queue's), so a retry succeeds wherever a new context would, and a
+ * call that succeeds after retries leaves sz4_last_error empty.
  *
  *   d_in, d_out   device pointers (d_out capacity out_cap bytes)
  *   block_size    1 .. 4 MiB
@@ -393,6 +395,12 @@ int sz4_debug_matches(sz4_ctx* ctx, uint32_t* len, uint16_t* dist, uint64_t n);
 /* The same copy, but always of the match arrays themselves: at levels > 3 what the parse was given
  * (at levels 4..6 after the greedy/lazy skip bookkeeping), whatever stage the run stopped after. */
 int sz4_debug_parse_input(sz4_ctx* ctx, uint32_t* len, uint16_t* dist, uint64_t n);
+/* Diagnostics of the device memory accounting, for the tests of the out-of-memory paths: out[0] = buffer
+ * growths that reached the allocator since the context was created, out[1] = growths an injected failure
+ * hit (the test hooks SZ4_TEST_ALLOC_CAP / SZ4_TEST_FAIL_RESERVE, read by sz4_create),
+ * out[2] = out-of-memory retries at a smaller piece in the last sz4_compress_blocks_device or batch
+ * compression call, out[3] = the smallest piece size in bytes that call cut a pipeline run for. */
+int sz4_debug_memory(sz4_ctx* ctx, uint64_t out[4]);
 
 /* ---- decoder: the reference's smallz4cat ------------------------------------------------------
  * Decompress an LZ4 frame with the semantics of the reference decoder

@@ -820,6 +820,17 @@ class Compressor:
         self._check(getattr(self._lib, name)(self._h, ln.ctypes.data, ds.ctypes.data, n), name)
         return ln, ds
 
+    def debug_memory(self) -> dict:
+        """The accounting's diagnostics (sz4_debug_memory): buffer growths and injected allocation failures
+        since the context was created, and the last blocks or batch call's piece retries and smallest piece."""
+        arr = (ctypes.c_uint64 * 4)()
+        self._check(self._lib.sz4_debug_memory(self._h, arr), "sz4_debug_memory")
+        return dict(zip(("growths", "injected", "retries", "min_piece"), (int(x) for x in arr)))
+
+    def last_error(self) -> str:
+        """The message of the last call's error ("" when it had none) (sz4_last_error)."""
+        return self._lib.sz4_last_error(self._h).decode()
+
     def device_bytes(self) -> int:
         """Device memory held by this context (scratch, staging, output buffers)."""
         return int(self._lib.sz4_device_bytes(self._h))

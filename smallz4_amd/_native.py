@@ -86,6 +86,7 @@ SIGNATURES = {
     "sz4_debug_stop_after": (None, [_vp, _i32]),
     "sz4_debug_matches": (_i32, [_vp, _vp, _vp, _u64]),
     "sz4_debug_parse_input": (_i32, [_vp, _vp, _vp, _u64]),
+    "sz4_debug_memory": (_i32, [_vp, ctypes.POINTER(_u64)]),
     "sz4_unlz4": (_i32, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64)]),
     "sz4_unlz4_device": (_i32, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64), _vp]),
     "sz4_device_bytes": (_u64, [_vp]),

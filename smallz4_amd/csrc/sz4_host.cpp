@@ -239,6 +239,8 @@ struct sz4_ctx {
   uint64_t batchChunk = kBatchChunkDefault;  // sz4_compress_blocks_device: input bytes per internal pipeline run
   bool batchChunkSet = false;          // set explicitly (sz4_set_batch_chunk, SZ4_BATCH_CHUNK): no free-memory cap
   bool batchChunked = false;           // the last sz4_compress_blocks_device call ran in several pieces
+  uint64_t pieceRetries = 0;           // sz4_debug_memory: the last blocks or batch call's out-of-memory retries
+  uint64_t pieceMin = 0;               // ... and the smallest piece size (bytes) a pipeline run of it was cut for
   // stream path, chunk continuation: the previous chunk's last block's final shortcut intervals
   // (ghost slot nblocks of iv/ivCount, B.prev of the first block), uploaded by runs whose RunMode says so
   std::vector<Interval> ghostIv;
@@ -288,6 +290,20 @@ struct sz4_ctx {
     else snprintf(buf, sizeof buf, "%s", what);
     err = buf;
     return code;
+  }
+
+  // before a blocks or batch piece is tried again at a smaller size: the failed attempt is no error of the
+  // call, and what it reserved goes back first -- the buffers it grew in order, up to the one that failed,
+  // carry the current call's mark, so shed() would keep them and the smaller piece would have to fit beside
+  // the larger one's.  Nothing runs on them: every earlier piece of the call has finished.  Afterwards the
+  // retry finds what a fresh context would (queues keep their held scratch)
+  void retry_smaller()
+  {
+    err.clear();
+    for (DevBuf* b : budget.bufs)
+      if (!b->held) b->release();
+    pipe.uploadedVersion = ~0ull;
+    pieceRetries++;
   }
 };
 
@@ -1107,7 +1123,9 @@ uint64_t piece_bytes(sz4_ctx* c)
     chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(kPieceFloor, c->budget.limit / 64));
   } else if (!c->batchChunkSet) {
     size_t freeB = 0, totalB = 0;
-    if (hipMemGetInfo(&freeB, &totalB) == hipSuccess)
+    hipError_t e = hipMemGetInfo(&freeB, &totalB);
+    if (c->budget.testFreeBytes) freeB = c->budget.testFreeBytes;  // tests: a device with this much free memory
+    if (e == hipSuccess)
       chunk = std::min<uint64_t>(chunk, std::max<uint64_t>(kPieceFloor, (freeB + c->budget.used) / (4 * kScratchPerByte)));
     else
       (void)hipGetLastError();
@@ -1282,6 +1300,15 @@ int sz4_create(sz4_ctx** ctx, int device, uint64_t reserve_bytes)
     const uint64_t v = strtoull(sc, nullptr, 10);
     if (v >= (1u << 20)) c->streamChunk = v;
   }
+  // tests: allocation failures injected into the accounting, and the free memory the piece sizing assumes
+  // (sz4_mem.h; sz4_debug_memory reports what they did)
+  auto hook = [](const char* name) {
+    const char* v = getenv(name);
+    return v ? (uint64_t)strtoull(v, nullptr, 10) : 0ull;
+  };
+  c->budget.testAllocCap = hook("SZ4_TEST_ALLOC_CAP");
+  c->budget.testFailReserve = hook("SZ4_TEST_FAIL_RESERVE");
+  c->budget.testFreeBytes = hook("SZ4_TEST_FREE_BYTES");
   for (auto& e : c->ev) hipEventCreate(&e);
   for (auto& e : c->evGather) hipEventCreate(&e);
   for (auto& e : c->evMerge) hipEventCreate(&e);
@@ -1415,6 +1442,8 @@ int sz4_compress_blocks_device(sz4_ctx* c, const void* d_in, uint64_t n, uint32_
     endMark = false;
   }
   c->batchChunked = false;
+  c->pieceRetries = 0;
+  c->pieceMin = ~0ull;
   if (n == 0) {
     if (out_cap < hl + (endMark ? 4 : 0)) return c->fail(SZ4_E_CAPACITY, "output buffer too small");
     if (hl) hipMemcpyAsync(d_out, hdr, hl, hipMemcpyHostToDevice, s);
@@ -1430,7 +1459,8 @@ int sz4_compress_blocks_device(sz4_ctx* c, const void* d_in, uint64_t n, uint32_
   // Without a bound the default piece is capped so that its scratch (< kScratchPerByte per piece byte) takes at
   // most a quarter of the memory this context could use now (free + what it holds): a GPU shared with a
   // caching allocator gets smaller pieces instead of SZ4_E_NOMEM.  A piece whose reservation still fails is
-  // halved and retried, down to kPieceFloor
+  // halved and retried, down to kPieceFloor; the failed attempt's buffers are released first and
+  // its error message cleared (sz4_ctx::retry_smaller)
   const uint64_t chunk = piece_bytes(c);
   // equal pieces (the last one is not a small remainder): ceil(n / chunk) of them, whole blocks each
   const uint64_t nPieces = (n + chunk - 1) / std::max<uint64_t>(chunk, 1);
@@ -1449,10 +1479,12 @@ int sz4_compress_blocks_device(sz4_ctx* c, const void* d_in, uint64_t n, uint32_
     if (rr == SZ4_E_NOMEM && piece > block_size && piece > kPieceFloor) {
       // smaller pieces: the next iteration re-plans this offset with half the piece
       piece = std::max<uint64_t>(block_size, std::max<uint64_t>(kPieceFloor, piece / 2) / block_size * block_size);
-      off -= piece;  // the loop adds it back
+      c->retry_smaller();
+      off -= piece;  // the loop adds it back (at offset 0 through the wrap)
       continue;
     }
     if (rr) return rr;
+    c->pieceMin = std::min(c->pieceMin, piece);
     // private padded copy: kernels read 4-byte windows that may run past the caller's buffer
     if ((e = hipMemcpyAsync(c->pipe.staged.p, (const uint8_t*)d_in + off, len, hipMemcpyDeviceToDevice, s)))
       return c->fail(SZ4_E_DEVICE, "stage input", e);
@@ -1491,6 +1523,7 @@ int64_t sz4_last_block_sizes(sz4_ctx* c, uint32_t* sizes, uint64_t max_blocks)
     return (int64_t)nb;
   }
   const uint64_t nb = std::min<uint64_t>(c->lastBlocks, max_blocks);
+  if (nb * 4 > c->pipe.blockBytes.cap) return SZ4_E_DEVICE;  // released since (a failed reservation, sz4_trim)
   if (nb && hipMemcpy(sizes, c->pipe.blockBytes.p, nb * 4, hipMemcpyDeviceToHost) != hipSuccess) return SZ4_E_DEVICE;
   for (uint64_t i = 0; i < nb; i++) sizes[i] &= 0x7FFFFFFFu;
   return (int64_t)nb;
@@ -1540,6 +1573,8 @@ static int compress_batch(sz4_ctx* c, const void* const* in_ptrs, const uint32_t
   c->batchChunked = true;
   c->lastBlocks = 0;
   c->gatherMs = 0;
+  c->pieceRetries = 0;
+  c->pieceMin = ~0ull;
   float stageSum[kStages] = {};
   // bounded memory: pieces of whole items in caller order, at most `piece` staged bytes and `cap` blocks each
   // (an item larger than the piece is a piece on its own); a piece whose scratch cannot be reserved is
@@ -1561,9 +1596,11 @@ static int compress_batch(sz4_ctx* c, const void* const* in_ptrs, const uint32_t
                               c->hostBytes.data(), stageSum, s);
     if (r == SZ4_E_NOMEM && blocks > 1 && piece > kPieceFloor) {
       piece = std::max<uint64_t>(kPieceFloor, piece / 2);
+      c->retry_smaller();
       continue;  // the same items again, in smaller pieces
     }
     if (r) return r;
+    c->pieceMin = std::min(c->pieceMin, piece);
     for (; i < j; i++) {
       pos += c->hostBytes[i];
       out_offsets[i + 1] = pos;
@@ -2036,6 +2073,16 @@ void sz4_set_timing(sz4_ctx* c, int on)
 void sz4_debug_stop_after(sz4_ctx* c, int stop_after)
 {
   if (c) c->stopAfter = stop_after;
+}
+
+int sz4_debug_memory(sz4_ctx* c, uint64_t out[4])
+{
+  if (!c || !out) return SZ4_E_ARG;
+  out[0] = c->budget.growths;
+  out[1] = c->budget.injected;
+  out[2] = c->pieceRetries;
+  out[3] = c->pieceMin == ~0ull ? 0 : c->pieceMin;
+  return SZ4_OK;
 }
 
 static int debug_copy(sz4_ctx* c, bool choices, uint32_t* len, uint16_t* dist, uint64_t n)

@@ -24,6 +24,20 @@ struct Budget {
   void (*onShed)(void*) = nullptr;
   void* owner = nullptr;
   inline uint64_t shed();  // releases every buffer the current call has not reserved; returns the bytes freed
+  // Test hooks, read once by sz4_create and inert at 0: they make a growth fail as an
+  // allocator's out-of-memory would, and change no size, plan or launch.  testAllocCap: a growth that would
+  // take `used` above it fails; testFailReserve: the growth with this number (counted from 1) fails, once.
+  uint64_t testAllocCap = 0;
+  uint64_t testFailReserve = 0;
+  uint64_t testFreeBytes = 0;  // the free device memory the batch piece sizing is to assume (it alone reads this)
+  uint64_t growths = 0;  // growths that reached the allocator since the budget was created
+  uint64_t injected = 0;  // ... of them, the ones whose first attempt a hook failed
+  // the allocator as a growth sees it; `inject`: this growth is testFailReserve's (all its attempts fail)
+  hipError_t alloc(void** p, size_t bytes, bool inject)
+  {
+    if (inject || (testAllocCap && used + bytes > testAllocCap)) return hipErrorOutOfMemory;
+    return hipMalloc(p, bytes);
+  }
 };
 
 // A grow-only device buffer.  It belongs to the budget it is constructed on and enters that budget's list
@@ -54,13 +68,18 @@ struct DevBuf {
     if (bud.limit) {
       if (bud.used - cap + want > bud.limit) want = bytes;
       if (bud.used - cap + want > bud.limit) bud.shed();
-      if (bud.used - cap + want > bud.limit) return hipErrorOutOfMemory;
+      if (bud.used - cap + want > bud.limit) {
+        release();  // a failed reserve leaves the buffer empty, whichever branch failed
+        return hipErrorOutOfMemory;
+      }
     }
     release();
-    hipError_t e = hipMalloc(&p, want);
+    const bool inject = ++bud.growths == bud.testFailReserve;
+    if (inject || (bud.testAllocCap && bud.used + want > bud.testAllocCap)) bud.injected++;
+    hipError_t e = bud.alloc(&p, want, inject);
     if (e == hipErrorOutOfMemory && bud.shed()) {
       (void)hipGetLastError();
-      e = hipMalloc(&p, want);
+      e = bud.alloc(&p, want, inject);
     }
     if (e == hipSuccess) {
       cap = want;
